@@ -2,6 +2,7 @@
 """bench.py - MIDI-VAE train-step (or decode) throughput on N MI355X (one process per GPU, RCCL over xGMI).
 
     python bench.py --gpus 1 --steps 20 --warmup 5                      (BASELINE configs[1], the default)
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full               (... and the side measurements listed below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W [--config 1|2|3|4]
 
@@ -25,14 +26,26 @@ policy runs the timed K steps; a probe that raises or whose pipeline times out i
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with these extra objects:
   roofline     dominant kernel (the T-step recurrent kernels) measured live with HIP events on the launch stream
+  elbo         (train configs) the loss after the warmup and after the last timed step
+A plain run does only that: set up, warm up, time the K steps, write the outputs (--dump-outputs), print the line.  With --full
+the line also carries what takes runs of its own:
   cpu_baseline the same step as float32 torch-CPU tensor operations on the host cores (oracle/torch_cpu.py), rank 0 / N=1 only,
                bounded sample, timed BEFORE the GPU phase
   fit_e2e      (N=1, the default run) the PRODUCT path a reference user calls: one 1024-window song per autoencoder.fit call on
                float64 one-hot lists at configs[1] - ms per optimizer step and windows/s including host conversion and upload
                (tools/fit_e2e_bench.py --json in a process of its own, after the headline region)
-  elbo         (train configs, rank 0 / N=1) the ELBO after each of K_e optimizer steps with a fresh epsilon per step on the first
-               16 windows of the bench's inputs: this engine (bf16, the timed schedule) beside float64 torch-CPU arithmetic
-               (oracle/torch_cpu.py elbo_trajectory, in the CPU subprocess phase), and their largest difference
+  other_configs (N=1, the default run) the other workloads, each in a process of its own after the headline region
+  elbo         (train configs, rank 0 / N=1) in addition the ELBO after each of K_e optimizer steps with a fresh epsilon per step
+               on the first 16 windows of the bench's inputs: this engine (bf16, the timed schedule) beside float64 torch-CPU
+               arithmetic (oracle/torch_cpu.py elbo_trajectory, in the CPU subprocess phase), and their largest difference
+
+--dump-outputs DIR writes what the timed path handed its caller in the last timed step as DIR/<name>.npy (float32 / float64):
+a train step's losses (metric.<key>.npy: the total loss, KL and every head's loss - the history values Keras' fit returns), a
+decode step's argmax note indices (note_indices.npy).  The inputs and initial parameters are seeded: the same arguments give the
+same inputs in every run, and these outputs agree from run to run to the rounding of the step's float32 sums.  Not dumped: the
+parameters after the K steps and the argmax hit rates.  The step's gradient sums are float32 atomics, so their order of summation
+differs from run to run; Keras-Adam turns that rounding into parameter steps of up to the learning rate wherever a gradient
+cancels to about zero (m / sqrt(v) is its sign there), and a window whose top two class scores tie within rounding flips its hit.
 """
 import argparse
 import json
@@ -266,6 +279,31 @@ def _plan_block(eng, **more):
                 refused_kinds={str(k)[:80]: str(v)[:120] for k, v in list(st["refused"].items())[:6]}, **more)
 
 
+DUMP_LIMIT_BYTES = 60 * 1000 * 1000        # (array data; with the .npy headers a dump stays under 64 MB)
+
+
+def dump_outputs(out_dir, eng, B, decode, metrics):
+    """--dump-outputs: what the timed path handed its caller in its last step - a train step's losses, a decode step's argmax note
+    indices (module docstring) - as float32 / float64 .npy files, at most DUMP_LIMIT_BYTES in all: an array over its share
+    of the limit is written as a fixed, seeded sample of its elements (flattened, indices in ascending order)"""
+    import numpy as np
+    arrays = {}
+    if decode:
+        arrays["note_indices"] = eng.note_indices(B).astype(np.float32)
+    else:
+        for k, v in metrics.items():
+            if k in ("loss", "kl") or k.endswith("_loss"):
+                arrays["metric.%s" % k] = np.asarray([v], dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            n = max(1, int(a.size * DUMP_LIMIT_BYTES // total))
+            if n < a.size:
+                a = a.reshape(-1)[np.sort(np.random.default_rng(1234).choice(a.size, n, replace=False))]
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -273,7 +311,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", type=int, default=1, choices=sorted(CONFIGS), help="index into BASELINE.json configs (module docstring)")
     ap.add_argument("--cell", default=None, choices=["LSTM", "GRU"], help="default: LSTM (north_star); GRU for --config 0")
-    ap.add_argument("--no-other-configs", action="store_true", help="N=1: skip the other workloads measured after the headline")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: the CPU baseline, the GPU-vs-CPU "
+                                                        "ELBO trajectory, the other workloads and fit_e2e (module docstring)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full, N=1: skip the other workloads measured after the headline")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--batch", type=int, default=0, help="windows per GPU (0 = the config's)")
     ap.add_argument("--seq-len", type=int, default=0)
@@ -281,8 +322,8 @@ def main():
     ap.add_argument("--latent", type=int, default=0)
     ap.add_argument("--prewarm-min", type=float, default=1.0, help="seconds of untimed passes before the warmup steps, at least")
     ap.add_argument("--prewarm-max", type=float, default=8.0, help="... at most (0 = none)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--elbo-steps", type=int, default=5, help="optimizer steps of the GPU-vs-CPU ELBO comparison (0 = none)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the ELBO comparison")
+    ap.add_argument("--elbo-steps", type=int, default=5, help="--full: optimizer steps of the GPU-vs-CPU ELBO comparison (0 = none)")
     ap.add_argument("--dp-overlap", type=int, default=-1,
                     help="N>1: reduce the decoder gradient bucket beside the encoder BPTT (dp.BucketedAllReduce); -1 = the product "
                          "policy (dp.DataParallel: on with RCCL and more than one rank)")
@@ -336,8 +377,8 @@ def main():
     spec = ModelSpec(cell=args.cell, H=args.hidden, Z=latent, Din=61, Dout=61, T=T, V=voices, ID=16, C=C, Le=2, Ld=2)
     device = "cuda:%d" % local
     # the CPU legs FIRST (rank 0, N=1 only): the GPU phase then runs last, undisturbed, and an idle-GPU sampler watching the
-    # process sees the GPU busy at the end of the run rather than idle
-    solo = world == 1 and rank == 0 and not args.no_cpu_baseline
+    # process sees the GPU busy at the end of the run rather than idle (--full only: a plain run times the headline alone)
+    solo = args.full and world == 1 and rank == 0 and not args.no_cpu_baseline
     cpu = cpu_baseline(spec, B) if (solo and not decode) else None
     EB = 16
     elbo_cpu = cpu_elbo(spec, EB, args.elbo_steps) if (solo and not decode and args.elbo_steps > 0) else None
@@ -521,6 +562,8 @@ def main():
     eng.prof = None
     m = eng.metrics(B) if not decode else None
     eng.check_pipeline()        # raises if a time-pipelined kernel ever gave up waiting for its producer (invalid results)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, B, decode, m)
 
     if rank == 0:
         G, H = spec.G, spec.H
@@ -620,8 +663,8 @@ def main():
                                 "('replayed'), the bracketed ones (every 4th: HIP events around the dominant launches, Engine._timed) included")
         if dp_stats is not None:
             out["dp"] = dp_stats
-        if world == 1 and not args.no_other_configs and args.config == 1 and args.dtype == "bf16" and not (args.batch or args.seq_len
-                                                                                                          or args.voices or args.latent):
+        if (args.full and world == 1 and not args.no_other_configs and args.config == 1 and args.dtype == "bf16"
+                and not (args.batch or args.seq_len or args.voices or args.latent)):
             # The other workloads, AFTER the headline region (which is exactly what it was without them), each in a process of its
             # own started from here: an engine built in a process that has already driven another engine's hardware queues runs
             # up to 14 % slower (measured at the reference's shape: 1.45 / 1.55 / 1.67 / 1.46 ms as the 1st .. 4th engine of one

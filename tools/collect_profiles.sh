@@ -2,9 +2,9 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r01l
 mkdir -p $O
-python $R/bench.py > $O/bench_lstm.json 2> $O/bench_lstm.err
-python $R/bench.py --cell GRU > $O/bench_gru.json 2> $O/bench_gru.err
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -- python $R/bench.py > /dev/null 2>&1
+python $R/bench.py --full > $O/bench_lstm.json 2> $O/bench_lstm.err
+python $R/bench.py --full --cell GRU > $O/bench_gru.json 2> $O/bench_gru.err
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -- python $R/bench.py --full > /dev/null 2>&1
 cp $(find /tmp/ks -name "*kernel_stats.csv" | head -1) $O/bench_lstm_kernel_stats.csv
 python $R/tools/timeline.py $(find /tmp/ks -name "*kernel_trace.csv" | head -1) --min-us 25 > $O/timeline_lstm_step.txt
 i=0
@@ -22,4 +22,4 @@ python $R/tools/gemm_microbench.py > $O/gemm_microbench.txt 2>&1
 python $R/tools/rnn_microbench.py --cell LSTM > $O/rnn_microbench.txt 2>&1
 python $R/tools/rnn_microbench.py --cell GRU >> $O/rnn_microbench.txt 2>&1
 python $R/tools/head_bench.py > $O/head_bench.txt 2>&1
-MVAE_BENCH_FORCE_DIST=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29519 $R/bench.py --gpus 1 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_lstm_one_rank_rccl.json
+MVAE_BENCH_FORCE_DIST=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29519 $R/bench.py --gpus 1 --full --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_lstm_one_rank_rccl.json

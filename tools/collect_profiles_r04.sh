@@ -8,7 +8,7 @@ cd $R
 want() { [ -z "$STEPS" ] || [[ " $STEPS " == *" $1 "* ]]; }
 if want 1; then
 # 1. the bench line (CPU baseline + float64 CPU ELBO first, then the GPU phase), LSTM and GRU; the other BASELINE configs; f32 parity mode
-python bench.py > $O/bench_lstm.json 2> $O/bench_lstm.err
+python bench.py --full > $O/bench_lstm.json 2> $O/bench_lstm.err
 python bench.py --cell GRU --no-cpu-baseline --no-other-configs > $O/bench_gru.json 2> $O/bench_gru.err
 python bench.py --config 2 --no-cpu-baseline --steps 10 --warmup 3 > $O/bench_config2_lstm.json 2> $O/bench_cfg.err
 python bench.py --config 2 --no-cpu-baseline --steps 10 --warmup 3 --cell GRU > $O/bench_config2_gru.json 2>> $O/bench_cfg.err

@@ -5,7 +5,7 @@ O=$R/gpurun_out/r05p; mkdir -p $O; cd $R
 want() { [ -z "$STEPS" ] || [[ " $STEPS " == *" $1 "* ]]; }
 if want 1; then
 # 1. the bench line (CPU baseline + float64 CPU ELBO first, then the GPU phase) with other_configs; GRU; f32 parity mode; one-rank RCCL with and without the early bucket
-python bench.py > $O/bench_lstm.json 2> $O/bench_lstm.err
+python bench.py --full > $O/bench_lstm.json 2> $O/bench_lstm.err
 python bench.py --cell GRU --no-cpu-baseline --no-other-configs > $O/bench_gru.json 2> $O/bench_gru.err
 python bench.py --dtype f32 --no-cpu-baseline --no-other-configs --steps 10 --warmup 3 > $O/bench_lstm_f32.json 2> $O/bench_lstm_f32.err
 MVAE_BENCH_FORCE_DIST=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus 1 --no-cpu-baseline --no-other-configs 2>/dev/null | tail -1 > $O/bench_lstm_one_rank_rccl.json

@@ -7,7 +7,7 @@ STEPS=${STEPS:-"1 2 3"}
 want() { [[ " $STEPS " == *" $1 "* ]]; }
 if want 1; then
 # 1. the bench line (CPU baseline + float64 CPU ELBO first, then the GPU phase, other_configs, fit_e2e); GRU with both kernel families; one-rank RCCL group (policy probe)
-python bench.py > $O/bench_lstm.json 2> $O/bench_lstm.err
+python bench.py --full > $O/bench_lstm.json 2> $O/bench_lstm.err
 python bench.py --cell GRU --no-cpu-baseline --no-other-configs > $O/bench_gru.json 2> $O/bench_gru.err
 MVAE_GRU_W8=0 python bench.py --cell GRU --no-cpu-baseline --no-other-configs > $O/bench_gru_4wave.json 2> $O/bench_gru_4wave.err
 MVAE_BENCH_FORCE_DIST=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus 1 --no-cpu-baseline --no-other-configs 2>/dev/null | tail -1 > $O/bench_lstm_one_rank_rccl.json
