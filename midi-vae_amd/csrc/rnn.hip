@@ -3,7 +3,7 @@
 // Replaces keras.layers.{GRU,LSTM,SimpleRNN} (reference vae_definition.py:448-480) and recurrentshop
 // {GRU,LSTM,SimpleRNN}Cell stepped by RecurrentModel (reference vae_definition.py:533-546 etc.).
 //
-// Mapping to the machine (generic kernel, any H in {64,128,256}):
+// Mapping to the machine (generic kernel, any H = 64 k for k = 1..8; shapes per H in fwd_nt / bwd_nt):
 //   * the recurrence is independent across batch rows, so ONE workgroup (4 waves) owns 16 batch rows for all
 //     T steps: no inter-workgroup synchronisation exists anywhere in this file;
 //   * per step the gate pre-activations are  gates^T (G*H x 16) = U^T (G*H x H) * h^T (H x 16)  on MFMA with
@@ -117,6 +117,12 @@ __global__ __launch_bounds__(NW * 64) void rnn_fwd_k(const mvae_rnn_fwd_args a) 
     constexpr int H = NT * 16 * NW, GH = G * H;
     constexpr int KG = op<WT>::KG, FE = op<WT>::FRAG_ELEMS, S = H / KG;
     constexpr int LDH = H + lds_pad<WT>::value;
+    // LSTM above H = 256: x_t W + b (G NT f32x4 per lane) is read after the MFMA stream instead of being held through it, and the
+    // stream ring is not carried across the gate arithmetic - with 2 waves per SIMD (or NT = 7) accumulators + ring + prefetched
+    // x + state do not fit the register file; the read latency is exposed once per step instead.  An f32 fragment feeds four
+    // MFMAs, so there half the ring covers the same time (and leaves room for the scalar mode's w / b rows)
+    constexpr bool LATE_X = CELL == MVAE_LSTM && H > 256;
+    constexpr int DEPTH = (LATE_X && sizeof(WT) == 4) ? STREAM_DEPTH / 2 : STREAM_DEPTH;
     typedef typename op<WT>::frag frag;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -166,6 +172,19 @@ __global__ __launch_bounds__(NW * 64) void rnn_fwd_k(const mvae_rnn_fwd_args a) 
     frag carry[STREAM_DEPTH];
     for (int t = 0; t < T; ++t) {
         const size_t row = (size_t)t * B + bb;
+        constexpr int GA = (CELL == MVAE_GRU) ? 2 : G;   // gates whose recurrent input is h itself
+        f32x4 acc[G][NT];
+        if constexpr (LATE_X) {     // h_{t-1} U before x_t W + b is read (the same stream as below, without the carried ring)
+#pragma unroll
+            for (int g = 0; g < G; ++g)
+#pragma unroll
+                for (int n = 0; n < NT; ++n) acc[g][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+            const WT* hrow = hbuf + cur * 16 * LDH + r * LDH + q * FE;
+            stream_mma<WT, S, GA * NT, DEPTH>(
+                wave_u, l * 16u, [](int s, int j) { return ((j / NT) * (H / 16) + j % NT) * S + s; },
+                [&](int s) { return *reinterpret_cast<const frag*>(hrow + s * KG); }, &acc[0][0]);
+        }
+
         // ---- x_t W + b for this lane's (gate, unit) positions; consumed after the MFMAs ----------------
         f32x4 xv[G][NT];
         if (XMODE == MVAE_X_DENSE) {
@@ -181,12 +200,17 @@ __global__ __launch_bounds__(NW * 64) void rnn_fwd_k(const mvae_rnn_fwd_args a) 
                 for (int n = 0; n < NT; ++n) xv[g][n] = st<WT>::load4(trow + g * H + ub[n]);
         } else if (XMODE == MVAE_X_SCALAR) {
             const float x = a.xs[row];
+            // (LATE_X: an offset hipcc cannot see through, so that the w / b rows are re-read from LDS every step instead of
+            //  being hoisted out of the time loop into 2 G NT more registers)
+            int zero = 0;
+            if constexpr (LATE_X) asm volatile("" : "+s"(zero));
+            const float* wbt = wb + zero;
 #pragma unroll
             for (int g = 0; g < G; ++g)
 #pragma unroll
                 for (int n = 0; n < NT; ++n) {
-                    const f32x4 w4 = *reinterpret_cast<const f32x4*>(wb + g * H + ub[n]);
-                    const f32x4 b4 = *reinterpret_cast<const f32x4*>(wb + GH + g * H + ub[n]);
+                    const f32x4 w4 = *reinterpret_cast<const f32x4*>(wbt + g * H + ub[n]);
+                    const f32x4 b4 = *reinterpret_cast<const f32x4*>(wbt + GH + g * H + ub[n]);
                     xv[g][n] = x * w4 + b4;
                 }
         } else {
@@ -198,21 +222,21 @@ __global__ __launch_bounds__(NW * 64) void rnn_fwd_k(const mvae_rnn_fwd_args a) 
         }
 
         // ---- h_{t-1} U on the matrix cores -----------------------------------------------------------
-        constexpr int GA = (CELL == MVAE_GRU) ? 2 : G;   // gates whose recurrent input is h itself
-        f32x4 acc[G][NT];
+        if constexpr (!LATE_X) {
 #pragma unroll
-        for (int g = 0; g < G; ++g)
+            for (int g = 0; g < G; ++g)
 #pragma unroll
-            for (int n = 0; n < NT; ++n) acc[g][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const WT* hrow = hbuf + cur * 16 * LDH + r * LDH + q * FE;
-        if constexpr (MVAE_STREAM_CARRY && CELL != MVAE_GRU && (S * GA * NT) % STREAM_DEPTH == 0)
-            stream_mma_carry<WT, S, GA * NT, STREAM_DEPTH>(
-                carry, t == 0, wave_u, l * 16u, [](int s, int j) { return ((j / NT) * (H / 16) + j % NT) * S + s; },
-                [&](int s) { return *reinterpret_cast<const frag*>(hrow + s * KG); }, &acc[0][0]);
-        else
-        stream_mma<WT, S, GA * NT, STREAM_DEPTH>(
-            wave_u, l * 16u, [](int s, int j) { return ((j / NT) * (H / 16) + j % NT) * S + s; },
-            [&](int s) { return *reinterpret_cast<const frag*>(hrow + s * KG); }, &acc[0][0]);
+                for (int n = 0; n < NT; ++n) acc[g][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+            const WT* hrow = hbuf + cur * 16 * LDH + r * LDH + q * FE;
+            if constexpr (MVAE_STREAM_CARRY && CELL != MVAE_GRU && (S * GA * NT) % STREAM_DEPTH == 0)
+                stream_mma_carry<WT, S, GA * NT, STREAM_DEPTH>(
+                    carry, t == 0, wave_u, l * 16u, [](int s, int j) { return ((j / NT) * (H / 16) + j % NT) * S + s; },
+                    [&](int s) { return *reinterpret_cast<const frag*>(hrow + s * KG); }, &acc[0][0]);
+            else
+                stream_mma<WT, S, GA * NT, STREAM_DEPTH>(
+                    wave_u, l * 16u, [](int s, int j) { return ((j / NT) * (H / 16) + j % NT) * S + s; },
+                    [&](int s) { return *reinterpret_cast<const frag*>(hrow + s * KG); }, &acc[0][0]);
+        }
 
         f32x4 hnew[NT];
         if (CELL == MVAE_GRU) {
@@ -489,14 +513,20 @@ int launch_fwd(const mvae_rnn_fwd_args& a, hipStream_t s) {
     MVAE_CHECK_LAUNCH();
     return MVAE_OK;
 }
+// unit tiles per wave x waves: the 4 SIMDs get equal shares of the H / 16 tiles; two waves per SIMD where they fit
 template <int CELL, typename WT, int XMODE>
 int fwd_nt(const mvae_rnn_fwd_args& a, hipStream_t s) {
     switch (a.H) {
         case 64: return launch_fwd<CELL, WT, XMODE, 1>(a, s);
         case 128: return launch_fwd<CELL, WT, XMODE, 2>(a, s);
+        case 192: return launch_fwd<CELL, WT, XMODE, 3>(a, s);
         case 256:
             if constexpr (sizeof(WT) == 4) return launch_fwd<CELL, WT, XMODE, 2, 8>(a, s);
             else return launch_fwd<CELL, WT, XMODE, 4>(a, s);
+        case 320: return launch_fwd<CELL, WT, XMODE, 5>(a, s);
+        case 384: return launch_fwd<CELL, WT, XMODE, 3, 8>(a, s);
+        case 448: return launch_fwd<CELL, WT, XMODE, 7>(a, s);
+        case 512: return launch_fwd<CELL, WT, XMODE, 4, 8>(a, s);
     }
     return MVAE_E_UNSUPPORTED;
 }
@@ -542,9 +572,14 @@ int bwd_nt(const mvae_rnn_bwd_args& a, hipStream_t s) {
     switch (a.H) {
         case 64: return launch_bwd<CELL, WT, 1>(a, s);
         case 128: return launch_bwd<CELL, WT, 2>(a, s);
+        case 192: return launch_bwd<CELL, WT, 3>(a, s);
         case 256:
             if constexpr (sizeof(WT) == 4) return launch_bwd<CELL, WT, 2, 8>(a, s);
             else return launch_bwd<CELL, WT, 4>(a, s);
+        case 320: return launch_bwd<CELL, WT, 5>(a, s);
+        case 384: return launch_bwd<CELL, WT, 3, 8>(a, s);
+        case 448: return launch_bwd<CELL, WT, 7>(a, s);
+        case 512: return launch_bwd<CELL, WT, 4, 8>(a, s);
     }
     return MVAE_E_UNSUPPORTED;
 }

@@ -20,6 +20,7 @@ import numpy as np
 
 GATES = {"GRU": 3, "LSTM": 4, "SimpleRNN": 1}
 NSTATE = {"GRU": 1, "LSTM": 2, "SimpleRNN": 1}
+LSTM_SIZES = tuple(64 * k for k in range(1, 9))   # hidden widths the recurrent kernels are built for (csrc/rnn.hip fwd_nt)
 _ALIGN = 64  # floats (256 B): every tensor starts on a boundary that keeps 16-byte vector access legal
 
 
@@ -216,8 +217,8 @@ def spec_from_create_kwargs(kw: dict) -> ModelSpec:
             raise ValueError("composer_decoder_at_instrument_output needs meta_instrument")
     if s.style:
         assert 0 < s.C <= min(s.Z, 64)
-    if s.H % 64 or s.H > 256:
-        raise NotImplementedError("lstm_size must be 64, 128 or 256 (got %d)" % s.H)
+    if s.H not in LSTM_SIZES:
+        raise NotImplementedError("lstm_size must be one of %s (got %d)" % (", ".join(map(str, LSTM_SIZES)), s.H))
     if s.attach:
         if not (0 < s.attach < min(s.Din, s.Dout)) or s.Din != s.Dout:
             raise ValueError("attach_dim must be the instrument columns appended to every notes row (input_dim == output_dim)")

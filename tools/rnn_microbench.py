@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Time the recurrent kernels alone (T steps, B rows, H=256 bf16) - us per step for every input mode.
-   python tools/rnn_microbench.py [--cell LSTM] [--T 512] [--B 256]"""
+"""Time the recurrent kernels alone (T steps, B rows, H=256 bf16 unless --H) - us per step for every input mode.
+   python tools/rnn_microbench.py [--cell LSTM] [--T 512] [--B 256] [--rowmajor [--H 512] [--f32]]"""
 import argparse
 import os
 import sys
@@ -17,6 +17,7 @@ ap.add_argument("--cell", default="LSTM")
 ap.add_argument("--T", type=int, default=512)
 ap.add_argument("--B", type=int, default=256)
 ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--H", type=int, default=256, help="hidden width (64 k, k = 1..8); other than 256 only the generic kernels exist")
 ap.add_argument("--rowmajor", action="store_true", help="generic kernels (row-major sequences)")
 ap.add_argument("--f32", action="store_true", help="the f32 parity mode: generic kernels, f32 sequences and f32 MFMA")
 ap.add_argument("--signal", type=int, default=0, help="publish every N steps in a counter like a pipelined producer (nobody waits)")
@@ -28,12 +29,12 @@ ap.add_argument("--phased", action="store_true", help="LSTM: phased resident ker
 ap.add_argument("--w8", action="store_true", help="GRU: the two-waves-per-SIMD kernels (seq_layout TILE16Q); forward only until the BPTT exists")
 a = ap.parse_args()
 cell = hl.CELL_CODE[a.cell]
-a.rowmajor = a.rowmajor or a.f32
+a.rowmajor = a.rowmajor or a.f32 or a.H != 256
 DT = hl.F32 if a.f32 else hl.BF16
 LAY = hl.ROWMAJOR if a.rowmajor else (hl.TILE16 if (a.phased or a.cell not in ("LSTM", "GRU")) else hl.TILE16P)
 if a.w8:
     LAY = hl.TILE16Q
-G, H, T, B = hl.GATES[cell], 256, a.T, a.B
+G, H, T, B = hl.GATES[cell], a.H, a.T, a.B
 GH = G * H
 dev = "cuda:0"
 bf = torch.float32 if a.f32 else torch.bfloat16
