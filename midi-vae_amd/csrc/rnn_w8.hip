@@ -1084,6 +1084,9 @@ __device__ __forceinline__ void lstm_bwd_w8_body(const mvae_rnn_bwd_args& a, con
         vm_wait<V_STEP - lbw_vm_before(HAS_EXT ? 26 : 18, HAS_EXT)>();
         pin8(qa[0]); pin8(qa[1]); pin8(qa[2]); pin8(qs);
         if (HAS_EXT) { pin1(qd[0]); pin1(qd[1]); }
+        // every wave's M phase reads the WHOLE da tile (B fragments over all of GH): no wave may overwrite it with this step's
+        // values before the slowest one has read the previous step's (without this barrier the error grew from T = 2 on)
+        w8_barrier();
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
             const f32x4 ig = n ? hi4(qa[0]) : lo4(qa[0]), fg = n ? hi4(qa[1]) : lo4(qa[1]), gg = n ? hi4(qa[2]) : lo4(qa[2]);

@@ -2,6 +2,13 @@
 
 Tolerances: f32 mode (exact-f32 MFMA, f32 storage) rtol/atol 2e-4 class against float64; bf16 mode (bf16 MFMA
 operands + bf16 sequence storage, f32 accumulate/state) 3e-2 class.  Integer outputs (argmax) are bit-exact.
+``close(got, want, tol)`` bounds |err| by tol * (1 + |want|): an absolute floor of tol, far above the recurrent kernels'
+gate gradients (~2.5e-3), dh0 / dc0 without an upstream gradient and the heads' d(logits) and dhs (~1/R) - a zero gradient
+passes it.  So the recurrent and head tests also check every output block by block at its own scale (tests/parity.py:
+per (time step, gate) for acts / da, per time step for hs / cs, per row for probabilities, d(logits) and dhs, the whole
+tensor for h_last / dh0 / dc0; elementwise against rtol |want| + floor * block RMS and normwise, one table of constants per
+mode), and the heads' loss to a relative 1e-4 (the oracle is given the kernel's rounded hs and W).  The bf16 constants
+come from a rounding model of a correct kernel and the margins measured on the MI355X (profiles/r08_parity_margins.txt).
 """
 import numpy as np
 import pytest
@@ -11,6 +18,7 @@ import midi_vae_amd  # noqa: F401
 from midi_vae_amd import hiplib as hl
 from midi_vae_amd import ops
 from oracle import vae_oracle as vo
+from tests import parity as par
 
 
 import contextlib
@@ -107,15 +115,7 @@ def close(got, want, tol, what=""):
         what, err.max(), tol, np.unravel_index(np.argmax(err - bound), err.shape))
 
 
-def _rnn_problem(cellname, H, T, B, seed, K=7):
-    rng = np.random.default_rng(seed)
-    G = vo.GATES[cellname]
-    U = rng.standard_normal((H, G * H)) * (0.5 / np.sqrt(H))
-    W = rng.standard_normal((K, G * H)) * 0.4
-    b = rng.standard_normal((G * H,)) * 0.2
-    h0 = rng.standard_normal((B, H)) * 0.3
-    c0 = rng.standard_normal((B, H)) * 0.3
-    return rng, G, U, W, b, h0, c0
+_rnn_problem = par.rnn_problem         # (shared with test_parity_cpu.py: the same problems on the CPU)
 
 
 def _paired8_columns(table):
@@ -218,6 +218,11 @@ def test_rnn_forward(cellname, cell, dtype, tol, xmode, H, B):
         close(host(h_last), hs_o[-1], tol, "h_last" + what)
         if cs is not None:
             close(host(cs), cs_o, tol, "cs" + what)
+        par.assert_parity(host(hs), hs_o, dtype, par.step_blocks, "hs" + what, values=True)
+        par.assert_parity(host(acts), acts_o, dtype, par.gate_blocks(cellname), "acts" + what, values=True)
+        par.assert_parity(host(h_last), hs_o[-1], dtype, par.whole, "h_last" + what, values=True)
+        if cs is not None:
+            par.assert_parity(host(cs), cs_o, dtype, par.step_blocks, "cs" + what, values=True)
 
 
 @pytest.mark.parametrize("xmode", ["dense", "index", "const"])
@@ -255,6 +260,12 @@ def test_gru_forward_two_waves_per_simd_short_odd_and_long(xmode, T):
             close(host(hs), hs_o, tol, "hs (%s)" % save)
         if acts is not None:
             close(host(tile16(acts, T * B, GH, False, paired="q")), acts_o, tol, "acts")
+        par.assert_parity(host(h_last), hs_o[-1], hl.BF16, par.whole, "h_last (%s)" % save, values=True)
+        if hs is not None:
+            par.assert_parity(host(hs), hs_o, hl.BF16, par.step_blocks, "hs (%s)" % save, values=True)
+        if acts is not None:
+            par.assert_parity(host(tile16(acts, T * B, GH, False, paired="q")), acts_o, hl.BF16, par.gate_blocks(cellname), "acts",
+                              values=True)
 
 
 def test_paired8_table_and_tile16q_relayout():
@@ -318,17 +329,10 @@ def test_lstm_backward_two_waves_per_simd_experiment_keeps_parity(T, ext, monkey
 
 
 def _rnn_backward_case(cellname, cell, dtype, tol, H, B, ext, T):
-    rng, G, U, W, b, h0, c0 = _rnn_problem(cellname, H, T, B, seed=11 + H)
-    GH = G * H
+    GH = vo.GATES[cellname] * H
     td = ops.torch_dtype(dtype)
     rnd = (lambda a: host(dev(a, td))) if dtype == hl.BF16 else (lambda a: a)
-    xp = rng.standard_normal((T, B, GH)) * 0.5
-    hs_o, cs_o, acts_o = vo.rnn_forward(cellname, xp, U, h0, c0 if cellname == "LSTM" else None)
-    hs_o, acts_o = rnd(hs_o), rnd(acts_o)
-    if cs_o is not None:
-        cs_o = rnd(cs_o)
-    dext = rnd(rng.standard_normal((T, B, H)) * 0.1) if ext else None
-    dlast = rng.standard_normal((B, H)) * 0.1
+    U, hs_o, cs_o, acts_o, dext, dlast = par.rnn_backward_problem(cellname, H, T, B, ext, rnd)
     da_o, dU_o, dh0_o, dc0_o = vo.rnn_backward(cellname, hs_o, cs_o, acts_o, U, dext, dlast)
 
     ut = ops.pack_recurrent(dev(U), cell, dtype, 1)
@@ -355,6 +359,10 @@ def _rnn_backward_case(cellname, cell, dtype, tol, H, B, ext, T):
             close(host(dc0), dc0_o, tol, "dc0" + what)
         if cellname == "GRU":
             close(host(rh), acts_o[:, :, H:2 * H] * hs_o[:-1], tol, "rh" + what)
+        par.assert_parity(host(da), da_o, dtype, par.gate_blocks(cellname), "da" + what)
+        par.assert_parity(host(dh0), dh0_o, dtype, par.whole, "dh0" + what)
+        if cellname == "LSTM":
+            par.assert_parity(host(dc0), dc0_o, dtype, par.whole, "dc0" + what)
 
 
 @pytest.mark.parametrize("ta,tb", [(False, False), (False, True), (True, False), (True, True)])
@@ -481,34 +489,45 @@ def test_gemm_onehot_table_gradient(dtype, tol):
 
 
 @pytest.mark.parametrize("dtype,tol", [(hl.F32, 2e-5), (hl.BF16, 2e-2)])
-@pytest.mark.parametrize("N", [61, 16, 3])
+@pytest.mark.parametrize("N", [61, 16, 3, 77, 128])
 def test_softmax_head(dtype, tol, N):
-    rng = np.random.default_rng(N)
-    R, H = 333, 64
+    """N = 77 and 128 (no padding column): the 8-tile instantiation ('1hot-instrument' input, attach_instruments)"""
+    _softmax_head_case(dtype, tol, N, H=64, R=333)
+
+
+@pytest.mark.parametrize("dtype,tol", [(hl.F32, 2e-5), (hl.BF16, 2e-2)])
+@pytest.mark.parametrize("N,H,R,two_hot,b_stride", [(61, 128, 333, False, 0), (128, 320, 333, False, 0), (77, 512, 333, False, 0),
+                                                    (61, 64, 65536 + 37, False, 0), (128, 128, 65536 + 37, True, 0),
+                                                    (77, 256, 333, True, 0), (61, 64, 16 * 21, False, 16), (128, 64, 16 * 21, True, 16)])
+def test_softmax_head_wide_long_two_hot_and_padding_rows(dtype, tol, N, H, R, two_hot, b_stride):
+    """H up to 512 (the k loop), R = 65536 + 37 rows (the bounded grid walks the rows again: the LDS stage tile is reused - a
+    T = 512 x B = 256 step has 131072), two-hot targets (target_idx2, 255 on some rows: attach_instruments) and padding rows
+    (b_stride / b_valid: rows b >= 11 of every 16 carry targets equal to their argmax and must not count as hits)"""
+    _softmax_head_case(dtype, tol, N, H=H, R=R, two_hot=two_hot, b_stride=b_stride, b_valid=11 if b_stride else 0)
+
+
+def _softmax_head_case(dtype, tol, N, H, R, two_hot=False, b_stride=0, b_valid=0):
+    rng, hs_h, W, bias, tgt, rw, tgt2 = par.softmax_head_problem(N, H, R, seed=N, two_hot=two_hot)
     td = ops.torch_dtype(dtype)
-    hs = dev(rng.standard_normal((R, H)), td)
-    W = rng.standard_normal((H, N)) * 0.3
-    bias = rng.standard_normal((N,)) * 0.1
-    tgt = rng.integers(0, N, (R,))
-    tgt[5] = 255                                  # all-zero target row
-    rw = rng.random((R,)) / R
+    hs = dev(hs_h, td)
     NP = ops.head_np(N)
     wt = torch.zeros((NP, H), dtype=td, device=DEV)
     ops.transpose_convert(dev(W), wt, n_pad=NP)
     Wq = host(wt)[:N].T
-    logits = host(hs) @ Wq + bias
-    p = vo.softmax(logits)
-    y = np.zeros((R, N))
-    ok = tgt < N
-    y[np.nonzero(ok)[0], tgt[ok]] = 1
-    want_loss = np.sum(rw * vo._cce(p, y) * ok)
-    want_dl = 0.7 * rw[:, None] * vo._cce_grad_logits(p, y)
+    counted = (np.arange(R) % b_stride < b_valid) if b_stride else np.ones(R, bool)
+    if b_stride:                                  # padding rows whose target IS their argmax: hits if they were counted
+        am_o = np.argmax(host(hs) @ Wq + bias, 1)
+        tgt[~counted] = am_o[~counted]
+        if two_hot:
+            tgt2[~counted] = 255
+    p, want_loss, want_dl, y = par.softmax_head_oracle(host(hs), Wq, bias, tgt, rw, 0.7, tgt2)
     probs = torch.zeros((R, N), device=DEV)
     am = torch.zeros((R,), dtype=torch.uint8, device=DEV)
     dl = torch.zeros((R, NP), dtype=td, device=DEV)
     sc = torch.zeros((2,), device=DEV)
     ops.head(0, dtype, R, H, N, hs, wt, dev(bias), target_idx=dev(tgt, torch.uint8), row_weight=dev(rw), grad_scale=0.7,
-             probs=probs, argmax=am, dlogits=dl, scalars=sc)
+             probs=probs, argmax=am, dlogits=dl, scalars=sc, b_stride=b_stride, b_valid=b_valid,
+             target_idx2=dev(tgt2, torch.uint8) if two_hot else None)
     torch.cuda.synchronize()
     close(host(probs), p, tol, "probs")
     close(host(dl)[:, :N], want_dl, tol, "dlogits")
@@ -516,8 +535,14 @@ def test_softmax_head(dtype, tol, N):
     close(host(sc)[0], want_loss, tol * 5, "loss")
     # argmax is bit-exact w.r.t. the probabilities the kernel itself returned (first maximum)
     assert np.array_equal(am.cpu().numpy(), np.argmax(probs.cpu().numpy(), axis=1).astype(np.uint8))
-    hits = np.sum(np.argmax(probs.cpu().numpy(), 1) == np.where(ok, tgt, 0))
-    assert host(sc)[1] == hits
+    # a hit: the first maximum is the target row's first hot column (index 0 for an all-zero row), on rows that count
+    match = np.argmax(probs.cpu().numpy(), 1) == np.argmax(y, 1)
+    assert host(sc)[1] == np.sum(match & counted)
+    if b_stride:
+        assert np.sum(match & ~counted) > R // 4
+    par.assert_parity(host(probs), p, dtype, par.row_blocks, "probs", values=True)
+    par.assert_parity(host(dl)[:, :N], want_dl, dtype, par.row_blocks, "dlogits")
+    par.assert_rel(host(sc)[0], want_loss, par.LOSS_RTOL, "loss")
 
 
 @pytest.mark.parametrize("dtype", [hl.F32, hl.BF16])
@@ -593,6 +618,10 @@ def test_sigmoid_head(dtype, tol):
     close(host(dl)[:, 0], rw * 2 * (p - y) * p * (1 - p), tol)
     close(host(sc)[0], np.sum(rw * (p - y) ** 2), tol * 5)
     assert host(sc)[1] == np.sum(np.round(probs.cpu().numpy()) == y.astype(np.float32))
+    par.assert_parity(host(probs)[:, None], p[:, None], dtype, par.row_blocks, "probs", values=True)
+    par.assert_parity(host(dl)[:, :1], (rw * 2 * (p - y) * p * (1 - p))[:, None], dtype, par.row_blocks, "dlogits")
+    assert np.all(host(dl)[:, 1:] == 0)
+    par.assert_rel(host(sc)[0], np.sum(rw * (p - y) ** 2), par.LOSS_RTOL, "loss")
 
 
 def test_latent_block():
@@ -977,11 +1006,10 @@ def test_gemm_multi_equals_the_single_launches():
 def test_head_fused_input_gradient(dtype, tol, kind, N):
     """mvae_head with wc / dhs: the gradient w.r.t. the h sequence, d(logits) W^T, comes out of the head launch in TILE16 -
     against float64 on the d(logits) the same launch returned (and the zero / padded weight copies of mvae_prepare_batch)."""
-    rng = np.random.default_rng(N + kind)
     R, H = 320, 256 if dtype == hl.BF16 else 64
+    hs_h, W, rw, bias, tgt = par.fused_head_problem(kind, N, H, R, seed=N + kind)
     td = ops.torch_dtype(dtype)
-    hs = dev(rng.standard_normal((R, H)) * 0.5, td)
-    W = rng.standard_normal((H, N)) * 0.3
+    hs = dev(hs_h, td)
     NP = ops.head_np(N)
     wt = torch.zeros((NP, H), dtype=td, device=DEV)
     wc = torch.full((H, NP), 7.0, dtype=td, device=DEV)
@@ -993,15 +1021,42 @@ def test_head_fused_input_gradient(dtype, tol, kind, N):
     dl = torch.zeros((R, NP), dtype=td, device=DEV)
     dhs = torch.zeros((R, H), dtype=td, device=DEV)
     sc = torch.zeros((2,), device=DEV)
-    rw = rng.random((R,)) / R
     if kind == 0:
-        ops.head(0, dtype, R, H, N, hs, wt, dev(rng.standard_normal((N,)) * 0.1), target_idx=dev(rng.integers(0, N, (R,)), torch.uint8),
+        ops.head(0, dtype, R, H, N, hs, wt, dev(bias), target_idx=dev(tgt, torch.uint8),
                  row_weight=dev(rw), grad_scale=0.7, dlogits=dl, scalars=sc, wc=wc, dhs=dhs)
     else:
-        ops.head(1, dtype, R, H, 1, hs, wt, dev(np.array([0.1])), target_val=dev(rng.random(R)), row_weight=dev(rw), grad_scale=1.0,
+        ops.head(1, dtype, R, H, 1, hs, wt, dev(bias), target_val=dev(tgt), row_weight=dev(rw), grad_scale=1.0,
                  dlogits=dl, scalars=sc, wc=wc, dhs=dhs)
     torch.cuda.synchronize()
     want = host(dl) @ host(wc).T                                   # (R,NP) (NP,H)
     got = host(tile16(dhs, R, H, False))
     assert np.abs(want).max() > 0
     close(got, want, tol, "dhs")
+    par.assert_parity(got, want, dtype, par.row_blocks, "dhs")
+    # ... and the d(logits) it came from against the oracle's
+    Wq = host(wt)[:N].T
+    if kind == 0:
+        want_dl = par.softmax_head_oracle(host(hs), Wq, bias, tgt, rw, 0.7)[2]
+    else:
+        p = vo.sigmoid(host(hs) @ Wq + bias)[:, 0]
+        want_dl = (rw * 2 * (p - tgt) * p * (1 - p))[:, None]
+    par.assert_parity(host(dl)[:, :N], want_dl, dtype, par.row_blocks, "dlogits")
+
+
+@pytest.mark.parametrize("dtype", [hl.F32, hl.BF16])
+def test_head_fused_input_gradient_refuses_h_above_256(dtype):
+    """dhs needs H <= 256: at H = 320 mvae_head reports MVAE_E_UNSUPPORTED and launches nothing - dhs and dlogits keep what
+    they held (the caller then runs the GEMM)"""
+    rng = np.random.default_rng(41)
+    R, H, N = 320, 320, 61
+    td = ops.torch_dtype(dtype)
+    NP = ops.head_np(N)
+    wt = dev(rng.standard_normal((NP, H)) * 0.1, td)
+    wc = dev(rng.standard_normal((H, NP)) * 0.1, td)
+    dl = torch.full((R, NP), 3.0, dtype=td, device=DEV)
+    dhs = torch.full((R, H), 5.0, dtype=td, device=DEV)
+    with pytest.raises(RuntimeError, match="MVAE_E_UNSUPPORTED"):
+        ops.head(0, dtype, R, H, N, dev(rng.standard_normal((R, H)), td), wt, dev(np.zeros(N)),
+                 target_idx=dev(rng.integers(0, N, (R,)), torch.uint8), grad_scale=1.0, dlogits=dl, wc=wc, dhs=dhs)
+    torch.cuda.synchronize()
+    assert torch.all(dhs == 5.0) and torch.all(dl == 3.0)
