@@ -9,6 +9,12 @@ per (time step, gate) for acts / da, per time step for hs / cs, per row for prob
 tensor for h_last / dh0 / dc0; elementwise against rtol |want| + floor * block RMS and normwise, one table of constants per
 mode), and the heads' loss to a relative 1e-4 (the oracle is given the kernel's rounded hs and W).  The bf16 constants
 come from a rounding model of a correct kernel and the margins measured on the MI355X (profiles/r08_parity_margins.txt).
+The GEMM and reduction tests keep their ``close`` / ``assert_allclose`` calls, sized for unrounded operands, and beside them hold
+every output to the f32 accumulation unit of its own element (parity.assert_product: c_acc units + half an ulp of a bf16 output,
+normwise, zero stays zero - constants from a CPU model of a correct accumulation, test_parity_gemm_cpu.py), and run every path
+once more on small-integer operands, where the result must be BIT-equal to float64 (parity.assert_bits).  The kernels of
+csrc/misc.hip and csrc/latent.hip have files of their own: test_small_ops_gpu.py, test_latent_ops_gpu.py.  Margins measured on
+the MI355X against the new bounds: profiles/r09_op_parity_margins.txt.
 """
 import numpy as np
 import pytest
@@ -381,16 +387,37 @@ def test_gemm(ta, tb, dtype, tol, M, N, K):
     ops.gemm(Ad, Bd, C, M, N, K, trans_a=ta, trans_b=tb, bias=dev(bias), act=hl.ACT_TANH, alpha=0.05)
     torch.cuda.synchronize()
     close(host(C), np.tanh(0.05 * want + bias), tol * 10, "tanh epilogue")
+    kind = "bf16" if dtype == hl.BF16 else "f32"
+    opA, opB, bias32 = (A.T if ta else A), (B.T if tb else B), host(dev(bias))
+    par.assert_elementwise(host(C), np.tanh(np.float64(np.float32(0.05)) * want + bias32), "tanh epilogue")
     # split-K atomic accumulate into an f32 C that already holds data
     C2 = torch.ones((M, N), device=DEV)
     ops.gemm(Ad, Bd, C2, M, N, K, trans_a=ta, trans_b=tb, accumulate=True, split_k=3)
     torch.cuda.synchronize()
     close(host(C2), 1.0 + want, tol * np.sqrt(K), "split-k")
+    par.assert_product(host(C2), 1.0 + want, par.product_unit(opA, opB, extra=[1.0]), kind, "split-k")
     if dtype == hl.BF16:
         C3 = torch.zeros((M, N), dtype=torch.bfloat16, device=DEV)
         ops.gemm(Ad, Bd, C3, M, N, K, trans_a=ta, trans_b=tb)
         torch.cuda.synchronize()
         close(host(C3), want, 2e-2 * np.sqrt(K), "bf16 out")
+        par.assert_product(host(C3), want, par.product_unit(opA, opB), kind, "bf16 out", out_bf16=True)
+    # exact-arithmetic operands: small integers, alpha a power of two - every summation order gives the same bits
+    Ai, Bi = par.integer_operands(rng, A.shape), par.integer_operands(rng, B.shape)
+    bi, ci = par.integer_operands(rng, (N,)), par.integer_operands(rng, (M, N))
+    wi = 0.5 * ((Ai.T if ta else Ai) @ (Bi.T if tb else Bi))
+    C4, C5 = torch.zeros((M, N), device=DEV), dev(ci)
+    ops.gemm(dev(Ai, td), dev(Bi, td), C4, M, N, K, trans_a=ta, trans_b=tb, bias=dev(bi), alpha=0.5)
+    ops.gemm(dev(Ai, td), dev(Bi, td), C5, M, N, K, trans_a=ta, trans_b=tb, accumulate=True, split_k=3, alpha=0.5)
+    torch.cuda.synchronize()
+    par.assert_bits(host(C4), wi + bi, "f32", "integers, store with bias")
+    par.assert_bits(host(C5), wi + ci, "f32", "integers, split-k")
+    if dtype == hl.BF16:
+        C6 = torch.zeros((M, N), dtype=torch.bfloat16, device=DEV)
+        ops.gemm(dev(Ai, td), dev(Bi, td), C6, M, N, K, trans_a=ta, trans_b=tb, alpha=0.5)
+        torch.cuda.synchronize()
+        assert np.mean(par.bf16_round(wi) != wi) > 0.1 or K < 64          # most elements need more than 8 bits: rounding shows
+        par.assert_bits(host(C6), wi, "bf16", "integers, bf16 out")
 
 
 @pytest.mark.parametrize("N", [1024, 768])
@@ -429,6 +456,7 @@ def test_weights_stationary_projection_equals_the_tiled_gemm(N, chunk_tiles, rev
     ref = host(A) @ host(W).T + host(bias)
     out = host(tile16(got, M, N, False) if lay == hl.TILE16 else got)
     close(out, ref, 2e-2 * np.sqrt(H) * 0.1 + 1e-2, "projection")
+    par.assert_product(out, ref, par.product_unit(host(A), host(W).T, extra=[host(bias)]), "bf16", "projection", out_bf16=True)
 
 
 @pytest.mark.parametrize("dtype", [hl.F32, hl.BF16])
@@ -470,6 +498,10 @@ def test_gemm_leading_dimensions_and_column_blocks():
     want = np.zeros((H, 3 * H))
     want[:, 2 * H:] = rh.T @ da[:, 2 * H:]
     close(host(dU), want, 1e-4)
+    rh, da = host(rh_d), host(da_d)                        # (the f32 values the kernel was handed)
+    unit = np.zeros((H, 3 * H))                            # the untouched column blocks: exactly zero
+    want[:, 2 * H:], unit[:, 2 * H:] = rh.T @ da[:, 2 * H:], par.product_unit(rh.T, da[:, 2 * H:])
+    par.assert_product(host(dU), want, unit, "f32", "dU column block")
 
 
 @pytest.mark.parametrize("dtype,tol", [(hl.F32, 1e-5), (hl.BF16, 1e-2)])
@@ -486,6 +518,16 @@ def test_gemm_onehot_table_gradient(dtype, tol):
     ops.gemm(dev(idx, torch.uint8), dad, out, D, N, R, trans_a=True, a_kind=hl.ONEHOT, accumulate=True, split_k=4)
     torch.cuda.synchronize()
     close(host(out), want, tol * 10)
+    A1 = np.zeros((R, D))
+    A1[np.arange(R), idx] = 1.0
+    par.assert_product(host(out), want, par.product_unit(A1.T, da), "bf16" if dtype == hl.BF16 else "f32", "table gradient")
+    dai = par.integer_operands(rng, (R, N))                # integers: exact in every order
+    outi = dev(par.integer_operands(np.random.default_rng(1), (D, N)))
+    wanti = host(outi) + 0.5 * (A1.T @ dai)
+    ops.gemm(dev(idx, torch.uint8), dev(dai, ops.torch_dtype(dtype)), outi, D, N, R, trans_a=True, a_kind=hl.ONEHOT, accumulate=True,
+             split_k=4, alpha=0.5)
+    torch.cuda.synchronize()
+    par.assert_bits(host(outi), wanti, "f32", "table gradient of integers")
 
 
 @pytest.mark.parametrize("dtype,tol", [(hl.F32, 2e-5), (hl.BF16, 2e-2)])
@@ -657,6 +699,7 @@ def test_latent_block():
     torch.cuda.synchronize()
     close(host(dmu), dmu_o, 1e-5)
     close(host(dlv), dlv_o, 1e-5)
+    # (at its own scale, with ldz / lddz, row weights, Z up to 256 and eps at epsilon_std = 1: tests/test_latent_ops_gpu.py)
 
 
 @pytest.mark.parametrize("N,ldx", [(1024, 1024), (256, 256), (64, 64), (8, 16), (61, 64), (1, 16)])
@@ -674,6 +717,9 @@ def test_colsum_bf16_vector_path_plain_and_weighted(N, ldx):
     Xh = host(X)[:, :N]
     close(host(out), 0.5 + Xh.sum(0), 2e-4 * np.sqrt(R))
     close(host(outw), (Xh * wgt[:, None].astype(np.float32)).sum(0), 2e-4 * np.sqrt(R))
+    w32 = wgt.astype(np.float32).astype(np.float64)
+    par.assert_product(host(out), 0.5 + Xh.sum(0), par.sum_unit(Xh, extra=[0.5]), "sum", "colsum")
+    par.assert_product(host(outw), w32 @ Xh, par.sum_unit(Xh, w32), "sum", "colsum_weighted")
 
 
 def test_prepare_batch_matches_single_calls():
@@ -707,6 +753,9 @@ def test_outer_bias_tile16():
     back = tile16(out, R, N, False)
     torch.cuda.synchronize()
     close(host(back), xs[:, None] * w[None] + b[None], 1e-2)
+    xs, w, b = (host(dev(a)) for a in (xs, w, b))          # (the f32 values the kernel was handed)
+    want = xs[:, None] * w[None] + b[None]                 # within half an ulp of bf16 plus two f32 units (the multiply, the add)
+    assert np.all(np.abs(host(back) - want) <= par.half_ulp_bf16(want) + 2.0 * par.product_unit(xs[:, None], w[None], extra=[b[None]]))
 
 
 def test_sum_over_time_split_and_accumulate():
@@ -722,6 +771,8 @@ def test_sum_over_time_split_and_accumulate():
     want = host(X).sum(0)
     close(host(out), want, 1e-4)
     close(host(acc), want, 1e-4)
+    par.assert_product(host(out), want, par.sum_unit(host(X)), "sum", "sum_over_time")
+    par.assert_product(host(acc), want, par.sum_unit(host(X)), "sum", "sum_over_time in two parts")
 
 
 def test_gemm_fast_narrow_n_accumulate():
@@ -737,6 +788,7 @@ def test_gemm_fast_narrow_n_accumulate():
     torch.cuda.synchronize()
     want = 1.0 + host(A).T.astype(np.float64) @ host(Bd)[:, :N].astype(np.float64)
     close(host(C), want, 2e-3 * np.sqrt(R) / 8)
+    par.assert_product(host(C), want, par.product_unit(host(A).T, host(Bd)[:, :N], extra=[1.0]), "bf16", "narrow N")
 
 
 def test_reductions_and_elementwise():
@@ -758,6 +810,13 @@ def test_reductions_and_elementwise():
     close(host(out2), host(dev(Xt, torch.bfloat16)).sum(0), 1e-5)
     close(host(dx), dy * (1 - y * y), 1e-6)
     close(host(tab), W + b, 1e-6)
+    X32 = host(dev(X))
+    par.assert_product(host(out), X32.sum(0), par.sum_unit(X32), "sum", "colsum f32")
+    Xt16 = host(dev(Xt, torch.bfloat16))
+    par.assert_product(host(out2), Xt16.sum(0), par.sum_unit(Xt16), "sum", "sum_over_time bf16")
+    y32, dy32 = host(dev(y)), host(dev(dy))
+    par.assert_elementwise(host(dx), dy32 * (1 - y32 * y32), "tanh_bwd")
+    par.assert_bits(host(tab), host(dev(W)) + host(dev(b)), "f32", "make_table: one f32 addition")
 
 
 def test_adam_keep_count_and_prep_add_i32_job():
@@ -843,6 +902,16 @@ def test_gemm_weight_gradient_with_fused_column_sums():
         A64, B64 = A.double().cpu().numpy(), Bf.double().cpu().numpy()[:, :N]
         np.testing.assert_allclose(C.cpu().numpy(), A64.T @ B64, rtol=2e-3, atol=2e-3 * np.sqrt(K))
         np.testing.assert_allclose(cs.cpu().numpy(), 0.25 + B64.sum(0), rtol=2e-3, atol=2e-3 * np.sqrt(K))
+        par.assert_product(host(C), A64.T @ B64, par.product_unit(A64.T, B64), "bf16", "C K=%d" % K)
+        par.assert_product(host(cs), 0.25 + B64.sum(0), par.sum_unit(B64, extra=[0.25]), "sum", "colsum_b K=%d" % K)
+        Ai, Bi = par.integer_operands(rng, (K, M)), par.integer_operands(rng, (K, ldb_))
+        Ci, csi = dev(par.integer_operands(rng, (M, N))), dev(par.integer_operands(rng, (N,)))
+        wC, wcs = host(Ci) + 0.25 * (Ai.T @ Bi[:, :N]), host(csi) + Bi[:, :N].sum(0)
+        ops.gemm(dev(Ai, torch.bfloat16), dev(Bi, torch.bfloat16), Ci, M, N, K, trans_a=True, ldb=ldb_, accumulate=True, split_k=sk,
+                 colsum_b=csi, alpha=0.25)
+        torch.cuda.synchronize()
+        par.assert_bits(host(Ci), wC, "f32", "C of integers K=%d" % K)
+        par.assert_bits(host(csi), wcs, "f32", "colsum_b of integers K=%d" % K)
 
 
 @pytest.mark.gpu
@@ -888,7 +957,21 @@ def test_gemm_k_streaming_follows_a_producer(onehot, live):
     np.testing.assert_allclose(C.cpu().numpy(), 0.5 + A64.T @ B64, rtol=2e-3, atol=2e-3 * np.sqrt(K))
     if not onehot:
         np.testing.assert_allclose(cs.cpu().numpy(), 0.25 + B64.sum(0), rtol=2e-3, atol=2e-3 * np.sqrt(K))
-    # argument checks: partitions must be whole 64-row k tiles, the grid must be resident, store mode is refused
+        par.assert_product(host(cs), 0.25 + B64.sum(0), par.sum_unit(B64, extra=[0.25]), "sum", "colsum_b")
+    par.assert_product(host(C), 0.5 + A64.T @ B64, par.product_unit(A64.T, B64, extra=[0.5]), "bf16", "C")
+    if not live:            # small-integer operands, counters already at their value: bit-equal to float64
+        Bi = par.integer_operands(rng, (K, N))
+        Ai = A64 if onehot else par.integer_operands(rng, (K, M))
+        Ci, csi = dev(par.integer_operands(rng, (M, N))), dev(par.integer_operands(rng, (N,)))
+        wC, wcs = host(Ci) + 0.5 * (Ai.T @ Bi), host(csi) + Bi.sum(0)
+        ops.gemm(A if onehot else dev(Ai, torch.bfloat16), dev(Bi, torch.bfloat16), Ci, M, N, K, trans_a=True, accumulate=True, split_k=P,
+                 a_kind=hl.ONEHOT if onehot else None, colsum_b=None if onehot else csi, k_wait=counters, k_wait_value=target,
+                 k_chunk_rows=rows, k_reverse=True, chunk_status=status, alpha=0.5)
+        torch.cuda.synchronize()
+        assert int(status.item()) == 0
+        par.assert_bits(host(Ci), wC, "f32", "C of integers")
+        if not onehot:
+            par.assert_bits(host(csi), wcs, "f32", "colsum_b of integers")
     lib = hl.load()
     with pytest.raises(RuntimeError):
         ops.gemm(A, Bf, C, M, N, K, trans_a=True, accumulate=True, split_k=3, a_kind=hl.ONEHOT if onehot else None,
@@ -935,7 +1018,9 @@ def test_gemm_k_streaming_multi_launch():
     A3[np.arange(K), idx.cpu().numpy()] = 1.0
     for C, A64 in ((C1, A1.double().cpu().numpy()), (C2, A2.double().cpu().numpy()), (C3, A3)):
         np.testing.assert_allclose(C.cpu().numpy(), A64.T @ B64, rtol=2e-3, atol=2e-3 * np.sqrt(K))
+        par.assert_product(host(C), A64.T @ B64, par.product_unit(A64.T, B64), "bf16", "C (M = %d)" % A64.shape[1])
     np.testing.assert_allclose(cs.cpu().numpy(), B64.sum(0), rtol=2e-3, atol=2e-3 * np.sqrt(K))
+    par.assert_product(host(cs), B64.sum(0), par.sum_unit(B64), "sum", "colsum_b")
     with pytest.raises(RuntimeError):       # more than 256 waiting workgroups in all
         ops.gemm_kstream_multi([ops.gemm(A1, Bf, C1, 256, N, K, split_k=16, **kw)] * 3)
     torch.cuda.synchronize()
@@ -977,6 +1062,24 @@ def test_gemm_multi_equals_the_single_launches():
     for k, w in want.items():
         np.testing.assert_allclose(multi[k].cpu().numpy(), w, rtol=2e-3, atol=2e-3 * np.sqrt(K), err_msg=k)
         np.testing.assert_allclose(multi[k].cpu().numpy(), single[k].cpu().numpy(), rtol=1e-4, atol=1e-3, err_msg=k)
+    units = dict(C1=np.concatenate([par.product_unit(A164.T, B64[:, :512]), par.product_unit(A264.T, B64[:, 512:])], 1),
+                 C2=par.product_unit(A264.T, B64), C3=par.product_unit(A164.T, Bn64[:, :61]), C4=par.product_unit(A3.T, B64),
+                 cs=par.sum_unit(B64))
+    for k, w in want.items():
+        for name, o in (("multi", multi), ("single", single)):
+            par.assert_product(host(o[k]), w, units[k], "sum" if k == "cs" else "bf16", "%s %s" % (name, k))
+    # small-integer operands: every partition and arrival order gives the same bits as float64
+    Ai1, Ai2, Bi, Bni = (par.integer_operands(rng, t.shape) for t in (A1, A2, Bf, Bn))
+    keep = A1, A2, Bf, Bn
+    A1, A2, Bf, Bn = bf(Ai1), bf(Ai2), bf(Bi), bf(Bni)     # (problems() reads these names)
+    exact = fresh()
+    assert ops.gemm_multi(problems(exact, True)) == 5
+    torch.cuda.synchronize()
+    A1, A2, Bf, Bn = keep
+    wanti = dict(C1=np.concatenate([Ai1.T @ Bi[:, :512], Ai2.T @ Bi[:, 512:]], 1), C2=Ai2.T @ Bi, C3=Ai1.T @ Bni[:, :61], C4=A3.T @ Bi,
+                 cs=Bi.sum(0))
+    for k, w in wanti.items():
+        par.assert_bits(host(exact[k]), w, "f32", "integers " + k)
     # more than 16 problems: two launches; every one accumulates into the same C
     C = torch.zeros((256, GH), device=DEV)
     assert ops.gemm_multi([ops.gemm(A2, Bf, C, 256, GH, K, trans_a=True, accumulate=True, split_k=2, build_only=True) for _ in range(20)]) == 20
@@ -1060,3 +1163,179 @@ def test_head_fused_input_gradient_refuses_h_above_256(dtype):
                  target_idx=dev(rng.integers(0, N, (R,)), torch.uint8), grad_scale=1.0, dlogits=dl, wc=wc, dhs=dhs)
     torch.cuda.synchronize()
     assert torch.all(dhs == 5.0) and torch.all(dl == 3.0)
+
+
+# ---- GEMM paths no other op test reaches (each against float64 on the rounded operands: tests/parity.py assert_product / assert_bits) ----
+def _operand(rng, rows, cols, ld, dt, integer, scale=1.0):
+    """a (rows, cols) operand inside rows of ``ld`` elements (the pad columns hold non-zero data too); device buffer, host values"""
+    a = par.integer_operands(rng, (rows, ld)) if integer else rng.standard_normal((rows, ld)) * scale
+    d = dev(a, dt)
+    return d, host(d)[:, :cols]
+
+
+def _gemm_case(M, N, K, a_dt, b_dt, c_dt=torch.float32, ta=False, tb=False, integer=False, alpha=1.0, bias=False, accumulate=False,
+               split_k=1, lda=None, ldb=None, ldc=None, seed=0, what="", **kw):
+    """one mvae_gemm call on random (unit bound) or small-integer operands (bit-equal); the columns of C beyond N must stay.
+    Mixed operand kinds run on the bf16 matrix cores: the reference rounds the f32 operand to bf16 first.  Returns C."""
+    rng = np.random.default_rng(seed + M + N + K)
+    ar, ac = (K, M) if ta else (M, K)
+    br, bc = (N, K) if tb else (K, N)
+    lda, ldb, ldc = lda or ac, ldb or bc, ldc or N
+    Ad, Ah = _operand(rng, ar, ac, lda, a_dt, integer)
+    Bd, Bh = _operand(rng, br, bc, ldb, b_dt, integer)
+    f32_path = a_dt == torch.float32 and b_dt == torch.float32
+    if not f32_path:
+        Ah, Bh = par.bf16_round(Ah), par.bf16_round(Bh)
+    opA, opB = (Ah.T if ta else Ah), (Bh.T if tb else Bh)
+    bias_h = host(dev(par.integer_operands(rng, (N,)) if integer else rng.standard_normal(N))) if bias else None
+    c0 = host(dev(par.integer_operands(rng, (M, ldc)) if integer else rng.standard_normal((M, ldc)), c_dt))
+    Cd = dev(c0, c_dt)
+    ops.gemm(Ad, Bd, Cd, M, N, K, trans_a=ta, trans_b=tb, lda=lda, ldb=ldb, ldc=ldc, bias=dev(bias_h) if bias else None,
+             accumulate=accumulate, split_k=split_k, alpha=alpha, **kw)
+    torch.cuda.synchronize()
+    al = np.float64(np.float32(alpha))
+    extra = ([bias_h] if bias else []) + ([c0[:, :N]] if accumulate else [])
+    want = al * (opA @ opB) + sum(extra)
+    storage = "bf16" if c_dt == torch.bfloat16 else "f32"
+    got = host(tile16(Cd, M, N, False)) if kw.get("c_layout") == hl.TILE16 else host(Cd)
+    par.assert_bits(got[:, N:], c0[:, N:], storage, what + ": columns beyond N")
+    if integer:
+        par.assert_bits(got[:, :N], want, storage, what + " (integers)")
+    else:
+        par.assert_product(got[:, :N], want, par.product_unit(opA, opB, al, extra), "f32" if f32_path else "bf16", what,
+                           out_bf16=storage == "bf16")
+    return Cd
+
+
+@pytest.mark.parametrize("ta,tb", [(False, False), (False, True), (True, False), (True, True)])
+@pytest.mark.parametrize("a_dt,b_dt", [(torch.bfloat16, torch.float32), (torch.float32, torch.bfloat16)])
+def test_gemm_mixed_operand_kinds(ta, tb, a_dt, b_dt):
+    """by_trans<bf16_t, MVAE_BF16, MVAE_F32> and its mirror: the f32 operand is rounded to bf16 on its way into LDS"""
+    for M, N, K in ((50, 61, 33), (300, 192, 256)):
+        _gemm_case(M, N, K, a_dt, b_dt, ta=ta, tb=tb, bias=True, what="mixed store")
+        _gemm_case(M, N, K, a_dt, b_dt, ta=ta, tb=tb, accumulate=True, split_k=3, what="mixed split-k")
+        _gemm_case(M, N, K, a_dt, b_dt, ta=ta, tb=tb, integer=True, alpha=0.5, bias=True, what="mixed store")
+        _gemm_case(M, N, K, a_dt, b_dt, ta=ta, tb=tb, integer=True, alpha=0.25, accumulate=True, split_k=3, what="mixed split-k")
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("K", [576, 2304])
+def test_gemm_store_mode_splits_k_by_itself_only_into_a_packed_c(dt, K):
+    """a store-mode f32 GEMM with K >= 512, at most 32 tiles and ldc == N zeroes C and runs split-K over atomics, the bias added by
+    partition 0 alone; with ldc > N it must not (the memset would not fit the rows) - the same answer either way, and with
+    integers the same bits"""
+    M, N = 16, 64
+    for integer, alpha in ((False, 1.0), (True, 0.5)):
+        a = _gemm_case(M, N, K, dt, dt, bias=True, integer=integer, alpha=alpha, what="automatic split-K")
+        b = _gemm_case(M, N, K, dt, dt, bias=True, integer=integer, alpha=alpha, ldc=N + 4, what="ldc > N")
+        if integer:
+            assert torch.equal(a, b[:, :N])
+
+
+@pytest.mark.parametrize("accumulate", [False, True])
+def test_gemm_persistent_tile_loop_under_max_blocks(accumulate):
+    """max_blocks below the tile count: gemm_k (f32, 64 x 64 tiles) and gemm_fast_k (bf16, 128 x 128 tiles) walk the tiles in a
+    loop - 1, 3 and tiles - 1 workgroups, store and split-K accumulate; sys_release on one case of each"""
+    sk = 2 if accumulate else 1
+    for (M, N, K, dt, tiles) in ((300, 192, 256, torch.float32, 15), (384, 256, 512, torch.bfloat16, 6)):
+        for mb in (1, 3, tiles * sk - 1):
+            for integer, alpha in ((False, 1.0), (True, 0.5)):
+                _gemm_case(M, N, K, dt, dt, tb=True, bias=not accumulate, accumulate=accumulate, split_k=sk, integer=integer, alpha=alpha,
+                           max_blocks=mb, sys_release=(mb == 3), what="max_blocks=%d" % mb)
+
+
+@pytest.mark.parametrize("path", ["fast", "generic"])
+def test_gemm_alpha_and_system_scope_release(path):
+    """alpha = 0.37 with sys_release = 1 on the fast (bf16, 128-multiples) and on the generic kernel (f32 output and bf16 output)"""
+    M, N, K = (256, 256, 512) if path == "fast" else (300, 192, 256)
+    for c_dt in (torch.float32, torch.bfloat16):
+        _gemm_case(M, N, K, torch.bfloat16, torch.bfloat16, c_dt=c_dt, tb=True, alpha=0.37, bias=True, sys_release=True, what=path)
+    _gemm_case(M, N, K, torch.bfloat16, torch.bfloat16, ta=True, alpha=0.37, accumulate=True, split_k=4, sys_release=True, what=path)
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+def test_gemm_tile16_output_with_bias_equals_the_row_major_run(dt):
+    """the TILE16 epilogue (f32: generic kernel; bf16: fast kernel) with bias and alpha, bit for bit the row-major result"""
+    M, N, K = 320 if dt == torch.float32 else 384, 192 if dt == torch.float32 else 256, 128
+    for integer, alpha in ((False, 0.37), (True, 0.5)):
+        rm = _gemm_case(M, N, K, dt, dt, c_dt=dt, tb=True, bias=True, alpha=alpha, integer=integer, what="row-major")
+        tl = _gemm_case(M, N, K, dt, dt, c_dt=dt, tb=True, bias=True, alpha=alpha, integer=integer, c_layout=hl.TILE16, what="TILE16")
+        assert torch.equal(tile16(tl, M, N, False), rm)
+
+
+@pytest.mark.parametrize("N", [8, 24, 61, 77, 120])
+def test_gemm_fast_narrow_n_pad_columns(N):
+    """one narrow N tile on the fast path (accumulate, row-contiguous B): ldb = N rounded up to 8 and ldb = 128.  Columns N up
+    to the next multiple of 8 belong to the last 16-byte load of a row and are zero, as the callers keep them; the columns beyond
+    hold non-zero data here: whatever the kernel does with them must not reach C"""
+    R, H = 1024, 256
+    rng = np.random.default_rng(N)
+    for ldb in ((N + 7) // 8 * 8, 128):
+        for integer, alpha in ((False, 1.0), (True, 0.5)):
+            Bm = par.integer_operands(rng, (R, ldb)) if integer else rng.standard_normal((R, ldb))
+            Bm[:, N:(N + 7) // 8 * 8] = 0
+            A = par.integer_operands(rng, (R, H)) if integer else rng.standard_normal((R, H))
+            Ad, Bd = dev(A, torch.bfloat16), dev(Bm, torch.bfloat16)
+            c0 = host(dev(par.integer_operands(rng, (H, N)) if integer else rng.standard_normal((H, N))))
+            C = dev(c0)
+            ops.gemm(Ad, Bd, C, H, N, R, trans_a=True, ldb=ldb, accumulate=True, split_k=4, alpha=alpha)
+            torch.cuda.synchronize()
+            want = c0 + alpha * (host(Ad).T @ host(Bd)[:, :N])
+            if integer:
+                par.assert_bits(host(C), want, "f32", "narrow N, ldb = %d" % ldb)
+            else:
+                par.assert_product(host(C), want, par.product_unit(host(Ad).T, host(Bd)[:, :N], extra=[c0]), "bf16", "narrow N, ldb = %d" % ldb)
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+def test_gemm_generic_kernel_edges(dt):
+    """gemm_k: a single element; K = 7 (under one 8-wide load); odd lda / ldb (the unaligned scalar-load branch of stage_tile), in
+    both storage orders; M x N on both sides of the switch to 128 x 128 tiles (M * N >= 256 * 1024); more split-K partitions than
+    k tiles (the empty ones are skipped)"""
+    for integer, alpha in ((False, 1.0), (True, 0.5)):
+        kw = dict(integer=integer, alpha=alpha)
+        _gemm_case(1, 1, 1, dt, dt, bias=True, what="1 x 1 x 1", **kw)
+        for ta, tb in ((False, False), (True, True)):
+            _gemm_case(5, 9, 7, dt, dt, ta=ta, tb=tb, bias=True, what="K = 7", **kw)
+            _gemm_case(50, 61, 33, dt, dt, ta=ta, tb=tb, lda=(50 if ta else 33) + 3, ldb=(33 if tb else 61) + 5, ldc=63, bias=True,
+                       what="odd leading dimensions", **kw)
+        _gemm_case(512, 512, 40, dt, dt, tb=True, bias=True, what="128-tiles", **kw)
+        _gemm_case(504, 512, 40, dt, dt, tb=True, bias=True, what="64-tiles", **kw)
+        _gemm_case(50, 61, 33, dt, dt, accumulate=True, split_k=8, what="empty split-K partitions", **kw)
+
+
+@pytest.mark.parametrize("K", [1024, 768])
+@pytest.mark.parametrize("lay", [hl.TILE16, hl.ROWMAJOR])
+@pytest.mark.parametrize("reverse", [False, True])
+def test_gemm_chunked_persistent_nt_equals_the_plain_gemm(K, lay, reverse):
+    """the persistent chunked mode on gemm_fast_k (not the weights-stationary kernel: K != 256) - the dX GEMM between two pipelined
+    layers, da (M, K) x W (256, K)^T: 1, 2 and 3 row blocks per workgroup and chunk on two workgroups, and the XCD-grouped order
+    (8 workgroups, 8 row blocks per chunk).  The chunk counters are at their wait value beforehand; the result is BIT-equal to
+    the same GEMM without chunking, every wave publishes every chunk, no wait times out."""
+    N = 256
+    rng = np.random.default_rng(K + lay)
+    for blocks, rb, nchunks in ((2, 1, 3), (2, 2, 3), (2, 3, 3), (8, 8, 2)):
+        rows = 128 * rb
+        M = rows * nchunks
+        A = dev(rng.standard_normal((M, K)) * 0.5, torch.bfloat16)
+        W = dev(rng.standard_normal((N, K)) * 0.1, torch.bfloat16)
+        want = torch.zeros((M, N), dtype=torch.bfloat16, device=DEV)
+        ops.gemm(A, W, want, M, N, K, trans_b=True, c_layout=lay)
+        ready = torch.full((nchunks,), 5, dtype=torch.int32, device=DEV)
+        done = torch.zeros((nchunks,), dtype=torch.int32, device=DEV)
+        status = torch.zeros(1, dtype=torch.int32, device=DEV)
+        got = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=DEV)
+        ops.gemm(A, W, got, M, N, K, trans_b=True, c_layout=lay, max_blocks=blocks, chunk_rows=rows, chunk_reverse=reverse,
+                 chunk_wait=ready, chunk_wait_value=5, chunk_done=done, chunk_status=status)
+        torch.cuda.synchronize()
+        assert torch.equal(got.view(torch.int16), want.view(torch.int16)), (blocks, rb)
+        assert int(status.item()) == 0 and done.tolist() == [4 * blocks] * nchunks
+        out = host(tile16(got, M, N, False) if lay == hl.TILE16 else got)
+        par.assert_product(out, host(A) @ host(W).T, par.product_unit(host(A), host(W).T), "bf16", "dX", out_bf16=True)
+        Ai, Wi = par.integer_operands(rng, (M, K)), par.integer_operands(rng, (N, K))            # integers: exact, then rounded once
+        goti = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=DEV)
+        ops.gemm(dev(Ai, torch.bfloat16), dev(Wi, torch.bfloat16), goti, M, N, K, trans_b=True, c_layout=lay, alpha=0.5, max_blocks=blocks,
+                 chunk_rows=rows, chunk_reverse=reverse, chunk_wait=ready, chunk_wait_value=5, chunk_status=status)
+        torch.cuda.synchronize()
+        par.assert_bits(host(tile16(goti, M, N, False) if lay == hl.TILE16 else goti), 0.5 * (Ai @ Wi.T), "bf16", "dX of integers")
+        assert int(status.item()) == 0
