@@ -167,7 +167,11 @@ int mvae_pack_recurrent(const float* U, void* out, int32_t cell, int32_t H, int3
  * GEMM  C = alpha * opA(A) * opB(B) [+ bias] [-> tanh]   (Dense layers :484,487,506-507,563-567; input
  * projections of stacked layers; all parameter gradients).  Row-major with leading dimensions.
  *   a_kind: MVAE_F32 / MVAE_BF16, or MVAE_A_ONEHOT: A is never stored - opA(A)[m,k] = (idx[k] == m)
- *           (requires trans_a = 1), used for the gradient of an X_INDEX table.
+ *           (requires trans_a = 1), used for the gradient of an X_INDEX table.  idx holds one byte per k; the fast
+ *           kernel takes M <= 256 (two 128-row tiles; rows >= M are computed and never stored).
+ *   Fast-kernel shapes (bf16 B, bf16 or one-hot A, K % 64 == 0): N a multiple of 128 - or, for an accumulating row-major
+ *           C += A^T B with row-contiguous B and no bias, ANY N: full 128-column tiles plus one narrow last tile
+ *           (ldb >= N rounded up to 8; the head dW with ldb = mvae_head_np(N)).  Everything else runs the generic kernel.
  *   c_kind: MVAE_F32 / MVAE_BF16.   accumulate: 0 store, 1 atomic add into f32 C (split-K allowed).
  * --------------------------------------------------------------------------------------------------------- */
 enum { MVAE_A_ONEHOT = 2 };
@@ -298,7 +302,7 @@ typedef struct {
     float grad_scale;             /* multiplies d(logits) (loss weight of the head)                          */
     float* probs;                 /* (R,N) f32 or NULL                                                       */
     uint8_t* argmax;              /* (R) or NULL: first-max index (kind 0), round(p) (kind 1)                */
-    void* dlogits;                /* (R,NP) dtype, NP = N rounded up to 16; required if want_grad            */
+    void* dlogits;                /* (R,NP) dtype, NP = mvae_head_np(N); required if want_grad; columns [N,NP) = 0 */
     float* scalars;               /* (2) accumulated atomically                                              */
     int32_t b_stride, b_valid;    /* rows are (t, b) with b = row % b_stride; rows with b >= b_valid are padding and
                                      are excluded from the metric count (0,0 = every row counts)             */
@@ -311,7 +315,8 @@ typedef struct {
                                      loss -log p[t1] - log p[t2], accuracy against the first hot column             */
 } mvae_head_args;
 int mvae_head(const mvae_head_args* a, void* stream);
-/* padded column count NP used for `wt` rows and `dlogits` columns of an N-wide head (16/32/64/128; <0 = too wide) */
+/* padded column count NP used for `wt` rows and `dlogits` columns of an N-wide head: 16 / 32 / 64 / 128 for N <= 128,
+ * 16 * ceil(N / 16) for N in (128, 192] (kind 0 only); < 0 = too wide: mvae_head then returns MVAE_E_UNSUPPORTED and launches nothing */
 int mvae_head_np(int32_t N);
 
 /* Latent block: KL term + reparameterisation + style classifier on z[:, :C], forward and backward

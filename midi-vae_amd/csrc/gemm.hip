@@ -224,7 +224,7 @@ __global__ __launch_bounds__(256) void gemm_k(const mvae_gemm_args a) {
 
 // ===========================================================================================================
 // Fast path: bf16 operands stored in bf16 (or one-hot A), 128x128 tiles, M%128 == N%128 == K%64 == 0, 16-byte
-// aligned rows.  Differences from the generic kernel above:
+// aligned rows (fast_ok: also a narrow LAST N tile of an accumulating A^T B, and a one-hot A of up to two M tiles).  Differences from the generic kernel above:
 //   * global -> LDS staging is a straight 16-byte copy (no float round trip), issued for tile k+1 BEFORE the MFMAs
 //     of tile k (register prefetch) into the other half of a double-buffered LDS image: one barrier per K tile;
 //   * BK = 64: 32 MFMAs per wave per barrier;
@@ -319,8 +319,8 @@ __device__ __forceinline__ void gemm_fast_body(const mvae_gemm_args a, const int
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, q = l >> 4, r = l & 15;
     const int wm = w >> 1, wn = w & 1;
     const int M = a.M, N = a.N, K = a.K;
-    const int tiles_n = (N + FBN - 1) / FBN, tiles_m = (M + FBM - 1) / FBM;   // M < 128: one-hot table gradient
-    const int nlim = B_RC ? (a.ldb < tiles_n * FBN ? a.ldb : 1 << 30) : 1 << 30;   // N < 128: head kernels (accumulate)
+    const int tiles_n = (N + FBN - 1) / FBN, tiles_m = (M + FBM - 1) / FBM;   // M % 128: one-hot table gradient (<= 2 M tiles)
+    const int nlim = B_RC ? (a.ldb < tiles_n * FBN ? a.ldb : 1 << 30) : 1 << 30;   // N % 128: head dW (accumulate); only the last N tile clamps
     const int splits = a.split_k > 1 ? a.split_k : 1;
     // persistent chunked mode: a fixed grid walks the M tiles chunk by chunk, handing over with device-side counters
     const int tiles_mc = a.chunk_rows ? a.chunk_rows / FBM : tiles_m;          // M tiles per chunk
@@ -874,11 +874,11 @@ bool fast_ok(const mvae_gemm_args& a) {
     const bool onehot = a.a_kind == MVAE_A_ONEHOT;
     if (!(a.b_kind == MVAE_BF16 && (a.a_kind == MVAE_BF16 || onehot))) return false;
     if (a.K % FBK) return false;
-    if (a.N % FBN) {    // one narrow N tile: row-contiguous B whose rows hold >= 8 columns, accumulate mode, no bias
-        if (!(a.N < FBN && !a.trans_b && a.accumulate && !a.bias && a.c_layout == MVAE_ROWMAJOR && a.ldb >= 8 &&
+    if (a.N % FBN) {    // a narrow last N tile: row-contiguous B whose rows hold >= 8 columns, accumulate mode, no bias
+        if (!(!a.trans_b && a.accumulate && !a.bias && a.c_layout == MVAE_ROWMAJOR && a.ldb >= 8 &&
               a.ldb >= ((a.N + 7) / 8) * 8)) return false;
     }
-    if (onehot) { if (a.M > FBM || !a.trans_a) return false; }          // one M tile; rows >= M are never hot
+    if (onehot) { if (a.M > 2 * FBM || !a.trans_a) return false; }      // one-byte row indices: two M tiles; rows >= M are never stored
     else if (a.M % FBM) return false;
     auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     if (!onehot && (!al16(a.A) || (a.lda % 8))) return false;

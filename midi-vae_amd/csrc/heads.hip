@@ -251,7 +251,18 @@ int launch(const mvae_head_args& a, hipStream_t s) {
         case 4: hipLaunchKernelGGL((head_k<WT, 4, KIND>), grid(head_rb<WT, 4, KIND>()), block, 0, s, a); break;
         case 5: case 6: case 7:
         case 8: hipLaunchKernelGGL((head_k<WT, 8, KIND>), grid(head_rb<WT, 8, KIND>()), block, 0, s, a); break;
-        default: return MVAE_E_UNSUPPORTED;
+        default:
+            // 9..12 tiles (softmax heads only; one-hot rows of the full MIDI range, plus the silent and the instrument-category
+            // columns): one instantiation per tile count - d(logits) has NP columns that the dW GEMM reads again at T*B rows
+            if constexpr (KIND == 0) {
+                if (ntl == 9) hipLaunchKernelGGL((head_k<WT, 9, KIND>), grid(1), block, 0, s, a);
+                else if (ntl == 10) hipLaunchKernelGGL((head_k<WT, 10, KIND>), grid(1), block, 0, s, a);
+                else if (ntl == 11) hipLaunchKernelGGL((head_k<WT, 11, KIND>), grid(1), block, 0, s, a);
+                else if (ntl == 12) hipLaunchKernelGGL((head_k<WT, 12, KIND>), grid(1), block, 0, s, a);
+                else return MVAE_E_UNSUPPORTED;
+                break;
+            }
+            return MVAE_E_UNSUPPORTED;
     }
     MVAE_CHECK_LAUNCH();
     return MVAE_OK;
@@ -259,14 +270,17 @@ int launch(const mvae_head_args& a, hipStream_t s) {
 
 }  // namespace
 
-// NB: dlogits has NP = 16*ceil(N/16) columns for N<=16 / N in (32,64] / (64,128]; N in (16,32] uses 32; the
-// kernel instantiation for 3 tiles is the 4-tile one, so callers must size wt / dlogits with mvae_head_np().
+// NB: dlogits has NP = 16 / 32 / 64 / 128 columns for N <= 16 / 32 / 64 / 128 (the kernel instantiation for 3 tiles is the
+// 4-tile one, ...), and NP = 16*ceil(N/16) for N in (128, 192]: the wide tile counts have an instantiation each, because every pad
+// column of dlogits is written once and read again by the dW GEMM at T*B rows (N = 129: 144 columns, not 192).  Callers must
+// size wt / dlogits with mvae_head_np().
 extern "C" int mvae_head_np(int32_t N) {
     const int ntl = (N + 15) / 16;
     if (ntl <= 1) return 16;
     if (ntl == 2) return 32;
     if (ntl <= 4) return 64;
     if (ntl <= 8) return 128;
+    if (ntl <= 12) return ntl * 16;
     return -1;
 }
 
@@ -276,7 +290,7 @@ extern "C" int mvae_head(const mvae_head_args* a, void* stream) {
     if (a->dhs && (!a->wc || !a->want_grad || (a->R % 16) || (a->H % 16))) return MVAE_E_ARG;
     if (a->dhs && a->H > 256) return MVAE_E_UNSUPPORTED;
     if (a->kind == 1 && a->N != 1) return MVAE_E_ARG;
-    if (a->kind == 0 && a->N > 128) return MVAE_E_UNSUPPORTED;
+    if (a->kind == 0 && a->N > 192) return MVAE_E_UNSUPPORTED;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (a->dtype == MVAE_F32) {
         if (a->H % 16) return MVAE_E_UNSUPPORTED;

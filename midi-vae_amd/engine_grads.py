@@ -72,7 +72,8 @@ class ParamGradients(object):
         """a weight-gradient GEMM C (M,N) f32 += A^T Bm (ops.gemm with trans_a, accumulate): launched now on the current stream -
         or, on a step that defers them (defer_grads_rows), kept as a problem of the one mvae_gemm_multi launch behind the last
         recurrence"""
-        if self._deferred_gemms is not None and self.tile16 and K % 64 == 0 and (N % 128 == 0 or N < 128):
+        # (the fast kernel's shapes: whole 128-column tiles, one narrow tile, or - a wide head's dW - whole tiles and a narrow last one)
+        if self._deferred_gemms is not None and self.tile16 and K % 64 == 0 and (N % 128 == 0 or N < 128 or kw.get("colsum_b") is None):
             self._deferred_gemms.append(ops.gemm(A, Bm, C, M, N, K, trans_a=True, accumulate=True, build_only=True, **kw))
             return
         ops.gemm(A, Bm, C, M, N, K, trans_a=True, accumulate=True, **kw)
@@ -228,7 +229,19 @@ class ParamGradients(object):
         if B > self.kstream_max_B:       # (a chunk's rows grow with the batch, the time the BPTT takes for it does not)
             return False
         free = (self.num_cus - self._resident_cus(layers, B, backward=True, side=True)) * self._occ["kstream"]
-        return free >= self.kstream_wgs * count
+        return free >= self.kstream_wgs * count + self._wide_table_wgs(layers, B)
+
+    def _wide_table_wgs(self, layers, B):
+        """resident workgroups of a stack's K-streaming launch beyond kstream_wgs per GEMM: the gradient of an input table of more
+        than one 128-row tile (one-hot rows wider than 128) has ceil(K / 128) x GH / 128 output tiles, times its partitions - the
+        second M tile doubles what kstream_wgs was sized for (a GRU's 2 x 6 tiles x 2 partitions: 24 workgroups, budgeted 16)"""
+        extra = 0
+        for r in layers:
+            if r.xmode == hl.X_INDEX and r.K > 128:
+                tiles = -(-r.K // 128) * -(-self.spec.GH // 128)
+                wgs = tiles * kstream_parts(tiles, self.pipe_chunk * B, self.kstream_rows, self.kstream_wgs)
+                extra += max(0, wgs - self.kstream_wgs)
+        return extra
 
     def _dec_kstream_ok(self, layers, B):
         """the decoder notes stack's weight gradients as a K-streaming launch behind its BPTT launch?  As _kstream_ok, for a stack

@@ -225,8 +225,10 @@ def spec_from_create_kwargs(kw: dict) -> ModelSpec:
         if s.bidirectional or s.meta_next or s.comp_notes:
             raise NotImplementedError("attach_instruments with a bidirectional encoder, the next-notes head or a classifier on the "
                                       "notes output")
-    if s.Dout > 128 or s.ID > 128 or s.Din > 255:
-        raise NotImplementedError("one-hot widths above 128 are not built")
+    # one-hot rows travel as one byte per row (255 = "no target"); the head kernels are built for up to 12 column tiles
+    for name, val, lim in (("output_dim", s.Dout, 192), ("meta_instrument_dim", s.ID, 192), ("input_dim", s.Din, 255)):
+        if val > lim:
+            raise NotImplementedError("%s=%d: one-hot outputs wider than 192 columns (inputs: 255) are not built" % (name, val))
     return s
 
 
