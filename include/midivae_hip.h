@@ -319,6 +319,46 @@ int mvae_head(const mvae_head_args* a, void* stream);
  * 16 * ceil(N / 16) for N in (128, 192] (kind 0 only); < 0 = too wide: mvae_head then returns MVAE_E_UNSUPPORTED and launches nothing */
 int mvae_head_np(int32_t N);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * 'choice' decode of a softmax head: Dense(H -> N) + softmax(logits / temperature) + one inverse-CDF draw per row with
+ * np.random.choice's rule (cdf = cumsum(q); cdf /= cdf[-1]; searchsorted(cdf, u, side='right')).  Replaces
+ * sample_vector(v, 'choice') (:1048-1067) on rows that stay on the device.  Forward only: one uint8 per row, nothing else.
+ * Up to `tries` draws per row, each from its own uniform; the first draw k with q_k > cutoff is kept, else the last one.
+ *
+ * Uniforms: `uniforms` (R, u_stride) f32 in [0,1) in the order of the rows of this launch, try i in column i - or NULL:
+ * generated, Philox4x32-10 with key = the 64-bit seed and counter = (global row low word, global row high word, head_id, 0);
+ * output word i is try i, u = (word >> 8) * 2^-24.  The GLOBAL row of device row g = row0 + (row of this launch) is the
+ * row's position in the caller's flattened (window, t) order:  (window0 + g % b_stride) * T + g / b_stride  for time-major
+ * rows (b_stride > 0), window0 * T + g for b_stride = 0 - so a window's draws depend neither on the batch it is decoded in
+ * nor on how a launch is sliced into row ranges.
+ *
+ * The per-call values (seed, first window, temperature, cutoff, tries) are read from `ctl`, a control block in DEVICE memory,
+ * when it is given: a recorded launch (step plans) then replays for any seed.  The caller validates such a block; the kernel
+ * clamps tries to 1..4 (and to u_stride).  With ctl = NULL they come from `host` and are validated here: temperature <= 0
+ * MVAE_E_ARG, tries > 4 MVAE_E_UNSUPPORTED.
+ * --------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    uint32_t seed_lo, seed_hi;          /* Philox key                                                         */
+    uint32_t window0_lo, window0_hi;    /* caller's index of the window in column b = 0 (64 bits)            */
+    float temperature, cutoff;          /* > 0; >= 0 (cutoff_sample_threshold)                                */
+    int32_t tries, reserved;            /* 1..4 (number_of_tries)                                             */
+} mvae_sample_ctl;
+typedef struct {
+    int32_t dtype;
+    int32_t R, H, N;              /* R rows of this launch                                                   */
+    const void* hs;               /* (R,H) dtype                                                             */
+    const void* wt;               /* (NP,H) dtype, NP = mvae_head_np(N): the head's own W^T copy             */
+    const float* bias;            /* (N)                                                                     */
+    const float* uniforms;        /* (R,u_stride) f32 or NULL = generated                                    */
+    const mvae_sample_ctl* ctl;   /* device memory, or NULL = `host`                                         */
+    uint8_t* out;                 /* (R) sampled column; pad rows (row % b_stride >= b_valid) hold anything  */
+    int32_t b_stride, b_valid;    /* as mvae_head_args (b_valid is informative: pad rows are computed too)   */
+    int32_t T, row0;              /* steps per window; device row of this launch's first row                 */
+    int32_t head_id, u_stride;    /* Philox counter word 2; values per row of `uniforms` (>= tries)          */
+    mvae_sample_ctl host;
+} mvae_head_sample_args;
+int mvae_head_sample(const mvae_head_sample_args* a, void* stream);
+
 /* Latent block: KL term + reparameterisation + style classifier on z[:, :C], forward and backward
  * (reference vae_definition.py:29-37, 498-502, 514-515, 730-734 and their gradients). */
 typedef struct {

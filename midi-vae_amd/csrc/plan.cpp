@@ -57,7 +57,7 @@ const entry k_entries[] = {
     MVAE_ENTRY(mvae_adam_step_dev), MVAE_ENTRY(mvae_rmsprop_step), MVAE_ENTRY(mvae_scalars_accumulate), MVAE_ENTRY(mvae_copy2d_f32),
     MVAE_ENTRY(mvae_history_from_latent), MVAE_ENTRY(mvae_signature_head_fwd), MVAE_ENTRY(mvae_signature_head_bwd),
     MVAE_ENTRY(mvae_softmax_bwd_add), MVAE_ENTRY(mvae_bi_concat), MVAE_ENTRY(mvae_add_time_reversed),
-    MVAE_ENTRY(mvae_event_record), MVAE_ENTRY(mvae_stream_wait_event),
+    MVAE_ENTRY(mvae_event_record), MVAE_ENTRY(mvae_stream_wait_event), MVAE_ENTRY(mvae_head_sample),
 };
 constexpr int k_max_slots = 16;
 

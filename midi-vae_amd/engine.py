@@ -25,6 +25,7 @@ import torch
 from . import hiplib as hl
 from . import ops
 from . import plan
+from . import sampling
 from .layout import ModelSpec, ParamLayout, init_params
 
 from .engine_io import ArrayStaging, Results
@@ -198,6 +199,7 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
         self._grad_streams = None        # (s_grad, s_grad2) unless overridden for a phase
         self._n_side = 0                 # recurrences running beside the stack being scheduled (residency, _pipelined)
         self._cur_B = self.maxB          # padded batch of the call being scheduled
+        self._sample_mode, self._want_vel = None, False      # a 'choice' decode in progress (Engine.decode): (heads with supplied uniforms, tries)
         self.num_cus = torch.cuda.get_device_properties(self.device).multi_processor_count
         self._occ = {k: max(1, hl.load().mvae_occupancy(i)) for i, k in enumerate(("dx", "proj", "kstream"))}
         self._chain_refused = False      # the library refused the fused latent chain once: steps key their plans by the exact window count
@@ -868,7 +870,7 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
                 self._fork_with_stack(self.dec_notes, *[h.stream for h in side])
         for h in side:
             with self._on(h.stream):
-                self._head_forward(h, B, Breal, states, tg, want_probs or h.name in aux_src, slot=None)
+                self._head_forward(h, B, Breal, states, tg, want_probs or h.name in aux_src or (h.kind == 1 and self._want_vel), slot=None)
         if not (multi and side and self.gate_side_heads):
             self._head_forward(self.head["notes"], B, Breal, states, tg, want_probs or "notes" in aux_src, slot=1)
         self._prefork = None
@@ -902,6 +904,7 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
                 self._rec_forward(r, B, start=start, **states(r))
         top = self._v(h.layers[-1].prefix + ".hs", h.T + 1, B, H)[1:]
         R = h.T * B
+        sampled = self._sample_mode is not None and h.kind == 0 and not tg and not self.training and h in self.dec_heads
         tgt = {}
         if tg:
             tgt = (dict(target_val=self._v(h.target, R)) if h.kind == 1 else dict(target_idx=self._v(h.target, R)))
@@ -918,6 +921,8 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
                 r0, r1 = i * Ts * B, (i + 1) * Ts * B
                 last = i == nsl - 1
                 def run():
+                    if sampled:          # ('choice' decode: the sampler in the head's place, slice by slice like it)
+                        return self._head_sample(h, top[i * Ts:(i + 1) * Ts], B, Breal, r0, r1)
                     ops.head(h.kind, self.kind, r1 - r0, H, h.N, top[i * Ts:(i + 1) * Ts], self._v(n + ".wt", h.NP, H), P[h.out + ".b"],
                              grad_scale=h.weight, probs=None, argmax=am[r0:r1], dlogits=None,
                              scalars=self.scal[h.slot:h.slot + 2], b_stride=B, b_valid=ops.ParamInt(Breal, ops.PARAM_B))
@@ -930,10 +935,25 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
                         run()
             self._join(self.s_grad, word=3)
             return
+        if sampled:
+            self._head_sample(h, top, B, Breal, 0, R)
+            if not want_probs:          # (nobody reads this head's probabilities: the sampler alone)
+                return
         ops.head(h.kind, self.kind, R, H, h.N, top, self._v(n + ".wt", h.NP, H), P[h.out + ".b"], grad_scale=h.weight,
                  probs=self._v("out.%s_p" % n, R, h.N) if want_probs else None, argmax=self._v(n + ".argmax", R),
                  dlogits=self._v(n + ".dl", R, h.NP) if (self.training and tg) else None, **self._fused_head_bwd(n, tg),
                  scalars=self.scal[h.slot:h.slot + 2], b_stride=B, b_valid=ops.ParamInt(Breal, ops.PARAM_B), **tgt)
+
+    def _head_sample(self, h, top, B, Breal, r0, r1):
+        """rows [r0, r1) of a softmax decoder head's 'choice' decode (mvae_head_sample): seed, first window, temperature, cutoff
+        and tries are read from the device control block (sample.ctl), so the recorded launch serves every later call"""
+        n, H = h.name, self.spec.H
+        supplied, tries = self._sample_mode
+        u = self.store[n + ".u"][:h.T * B * tries].view(h.T * B, tries)[r0:r1] if n in supplied else None
+        ops.head_sample(self.kind, r1 - r0, H, h.N, top, self._v(n + ".wt", h.NP, H), self.P[h.out + ".b"],
+                        self._v(n + ".choice", h.T * B)[r0:r1], uniforms=u, u_stride=tries if u is not None else 0,
+                        ctl=self.store["sample.ctl"], b_stride=B, b_valid=ops.ParamInt(Breal, ops.PARAM_B), T=h.T, row0=r0,
+                        head_id=sampling.HEAD_IDS[n])
 
     # ------------------------------------------------------------------------------------------------------
     # backward
@@ -1415,9 +1435,72 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
         self.encoder_forward(B)
         self._verify_pipeline(lambda: (self.scal.zero_(), self.encoder_forward(B)), key="encode")
 
-    def decode(self, B, want_probs=True):
-        """``decoder.predict`` on the staged [z|history]; argmax note indices are always produced on device."""
-        self._planned(("decode", B, float(self.norm_B), bool(want_probs)), lambda: self._decode(B, want_probs), params=self._call_params(B))
+    def decode(self, B, want_probs=True, sample=None, want_velocity=False):
+        """``decoder.predict`` on the staged [z|history]; argmax note indices are always produced on device.
+        ``sample``: a 'choice' decode (reference sample_vector(..., 'choice'), vae_definition.py:1048-1067) of every softmax head on
+        the device - a dict with ``temperature``, ``cutoff``, ``tries`` (1..4), ``seed`` (the Philox key of the generated uniforms),
+        ``first_window`` (the caller's index of window 0 of this batch) and optionally ``uniforms``: head name -> (B, T_head) or
+        (B, T_head, tries) values in [0, 1) that take the generated ones' place for that head.  Results: sampled_indices(B).
+        ``want_velocity``: the velocity head's output is kept (velocity(B)) although ``want_probs`` is off."""
+        kind = ("decode", B, float(self.norm_B), bool(want_probs))
+        self._want_vel = bool(want_velocity)
+        if want_velocity:
+            kind += ("velocity",)
+        if sample is None:
+            self._sample_mode = None
+        else:
+            if self.training:
+                raise RuntimeError("'choice' decode runs on forward-only engines")
+            kind += (self._stage_sample(B, sample),)
+        try:
+            self._planned(kind, lambda: self._decode(B, want_probs), params=self._call_params(B))
+        finally:
+            self._sample_mode, self._want_vel = None, False
+
+    def _stage_sample(self, B, sample):
+        """the staging copy of a 'choice' decode: the control block and the supplied uniforms (window-major -> time-major padded,
+        like every other input roll); returns the sample mode, the part of the plan key that decides which launches are made"""
+        tries = int(sample.get("tries", 1))
+        tau, cutoff = float(sample.get("temperature", 1.0)), float(sample.get("cutoff", 0.0))
+        if not 1 <= tries <= sampling.MAX_TRIES:
+            raise NotImplementedError("number_of_tries = %d: the device sampler draws 1..%d times per row" % (tries, sampling.MAX_TRIES))
+        if not tau > 0 or not cutoff >= 0:
+            raise ValueError("temperature must be > 0 and cutoff_sample_threshold >= 0")
+        words = sampling.control_words(sample.get("seed", 0), sample.get("first_window", 0), tau, cutoff, tries)
+        self.store["sample.ctl"].copy_(torch.from_numpy(words))
+        supplied = {}
+        for name, u in (sample.get("uniforms") or {}).items():
+            h = self.head[name]
+            if h.kind != 0 or h not in self.dec_heads:
+                raise ValueError("head %r is not a softmax decoder head" % name)
+            u = sampling.as_f32_uniforms(u).reshape(B, h.T, -1)
+            if u.shape[2] != tries:
+                raise ValueError("uniforms of head %r: %d values per row for %d tries" % (name, u.shape[2], tries))
+            if name + ".u" not in self.store:          # (allocated at the first use, for the widest call there can be)
+                self.store[name + ".u"] = torch.zeros(h.T * self.maxB * sampling.MAX_TRIES, dtype=torch.float32, device=self.device)
+            tm = np.zeros((h.T, self.pad16(B), tries), np.float32)
+            tm[:, :B] = u.transpose(1, 0, 2)
+            self._up(name + ".u", tm, torch.float32)
+            supplied[name] = True
+        self._sample_mode = (frozenset(supplied), tries if supplied else 0)
+        return ("choice",) + self._sample_mode
+
+    def sampled_indices(self, B):
+        """head name -> (B, T_head) uint8: what the last ``decode(..., sample=...)`` drew for every softmax decoder head"""
+        Bp = self.pad16(B)
+        return {h.name: self._v(h.name + ".choice", h.T, Bp)[:, :B].t().contiguous().cpu().numpy()
+                for h in self.dec_heads if h.kind == 0}
+
+    def argmax_indices(self, B):
+        """the same from the heads' own first-maximum indices (every decode without ``sample`` writes them)"""
+        Bp = self.pad16(B)
+        return {h.name: self._v(h.name + ".argmax", h.T, Bp)[:, :B].t().contiguous().cpu().numpy()
+                for h in self.dec_heads if h.kind == 0}
+
+    def velocity(self, B):
+        """(B, T) float32 output of the velocity head of the last decode run with ``want_probs`` or ``want_velocity``"""
+        h = self.head["vel"]
+        return self._v("out.vel_p", h.T, self.pad16(B))[:, :B].t().contiguous().cpu().numpy()
 
     def _decode(self, B, want_probs):
         self._have_targets = False

@@ -215,6 +215,14 @@ class Buffers(object):
         buf = self._alloc_common(B)
         st = self.store
         self.np_notes = self.head["notes"].NP
+        if not self.training:
+            # 'choice' decode (forward-only engines): the sampled column per row of every softmax decoder head, and the per-call
+            # values (mvae_sample_ctl: seed, first window, temperature, cutoff, tries) the staging copy of every such call writes -
+            # the recorded sampler launches only hold the block's address
+            for h in self.dec_heads:
+                if h.kind == 0:
+                    buf(h.name + ".choice", h.T * B, dtype=torch.uint8, device=dev)
+            st["sample.ctl"] = torch.zeros(8, dtype=torch.int32, device=dev)
         # encoder tail / latent / decoder initial states (all f32, (B, .) row-major)
         for name, n in (("cat", self.ncat * H), ("pack", H), ("extra", H), ("mu", Z), ("lv", Z), ("zh", s.zin),
                         ("style_p", max(s.C, 1)), ("S", self.n_init * H)):

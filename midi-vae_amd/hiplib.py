@@ -80,6 +80,21 @@ class HeadArgs(C.Structure):
                 ("scalars", _vp), ("b_stride", _i32), ("b_valid", _i32), ("wc", _vp), ("dhs", _vp), ("target_idx2", _vp)]
 
 
+class SampleCtl(C.Structure):
+    """per-call values of mvae_head_sample: in device memory (8 words, ``sampling.control_words``) or inside HeadSampleArgs"""
+    _fields_ = [("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("window0_lo", C.c_uint32), ("window0_hi", C.c_uint32),
+                ("temperature", _f32), ("cutoff", _f32), ("tries", _i32), ("reserved", _i32)]
+
+
+class HeadSampleArgs(C.Structure):
+    _fields_ = [("dtype", _i32), ("R", _i32), ("H", _i32), ("N", _i32), ("hs", _vp), ("wt", _vp), ("bias", _vp),
+                ("uniforms", _vp), ("ctl", _vp), ("out", _vp), ("b_stride", _i32), ("b_valid", _i32), ("T", _i32), ("row0", _i32),
+                ("head_id", _i32), ("u_stride", _i32), ("host", SampleCtl)]
+
+
+SAMPLE_MAX_TRIES = 4
+
+
 class LatentFwdArgs(C.Structure):
     _fields_ = [("B", _i32), ("Z", _i32), ("C", _i32), ("beta", _f32), ("prior_mean", _f32), ("prior_std", _f32),
                 ("inv_batch", _f32), ("mu", _vp), ("logvar", _vp), ("eps", _vp), ("style_target", _vp),
@@ -134,6 +149,7 @@ SIGNATURES = {
     "mvae_sum_over_time": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _vp]),
     "mvae_head": (_i32, [C.POINTER(HeadArgs), _vp]),
     "mvae_head_np": (_i32, [_i32]),
+    "mvae_head_sample": (_i32, [C.POINTER(HeadSampleArgs), _vp]),
     "mvae_latent_fwd": (_i32, [C.POINTER(LatentFwdArgs), _vp]),
     "mvae_latent_bwd": (_i32, [C.POINTER(LatentBwdArgs), _vp]),
     "mvae_latent_chain_fwd": (_i32, [C.POINTER(LatentChainFwdArgs), _vp]),

@@ -466,35 +466,118 @@ class Decoder(_ModelView):
                 i += 1
         return res
 
-    def _run(self, x, batch_size, want_probs=True):
+    def _run(self, x, batch_size, want_probs=True, sample=None, all_heads=False):
         """decoder forward over all windows at the forward-only engine's batch (``batch_size`` is the caller's: results are per
-        window); every rank decodes everything it is given - decoding is pure replicas"""
+        window); every rank decodes everything it is given - decoding is pure replicas.
+        ``sample``: the resolved arguments of a 'choice' decode (_sample_spec) - every engine batch is told the caller's index of
+        its first window, so a window's draws do not depend on the batches.  ``all_heads``: the third result is a dict head ->
+        indices of every softmax head (+ 'velocity')."""
         sp = self._s.spec
         a = self._unpack(x)
         z = np.asarray(a.pop("z"))
         n = z.shape[0]
         eng = self._s.get_infer(n)
-        outs, idxs = [], []
+        outs, idxs, heads = [], [], []
         for lo in range(0, n, eng.maxB):
             hi = min(n, lo + eng.maxB)
             B = hi - lo
             eng.stage_decoder_inputs(B, z=z[lo:hi], **{k: (None if v is None else np.asarray(v)[lo:hi]) for k, v in a.items()})
-            eng.decode(B, want_probs=want_probs)
+            if sample is None and not all_heads:
+                eng.decode(B, want_probs=want_probs)
+            else:
+                spec = None
+                if sample is not None:
+                    spec = dict(sample, first_window=lo, uniforms={k: u[lo:hi] for k, u in (sample.get("uniforms") or {}).items()})
+                eng.decode(B, want_probs=want_probs, sample=spec, want_velocity=all_heads and sp.meta_velocity)
             if want_probs:
                 outs.append(eng.outputs(B))
-            idxs.append(eng.note_indices(B))
+            if sample is None:
+                idxs.append(eng.note_indices(B))
+                if all_heads:
+                    heads.append(eng.argmax_indices(B))
+            else:
+                heads.append(eng.sampled_indices(B))
+                idxs.append(heads[-1]["notes"])
+            if all_heads and sp.meta_velocity:
+                heads[-1]["velocity"] = eng.velocity(B)
         eng.check_pipeline()
-        return outs, np.concatenate(idxs, 0) if idxs else np.zeros((0, sp.T), np.uint8)
+        notes = np.concatenate(idxs, 0) if idxs else np.zeros((0, sp.T), np.uint8)
+        if not all_heads:
+            return outs, notes
+        return outs, notes, ({k: np.concatenate([h[k] for h in heads], 0) for k in heads[0]} if heads else {})
 
     def predict(self, x, batch_size=32, verbose=0):
         outs, _ = self._run(x, batch_size)
         res = [np.concatenate([o[h] for o in outs], 0) for h in self._s.head_names()]
         return res if len(res) > 1 else res[0]
 
-    def predict_note_indices(self, x, batch_size=32):
-        """Fused argmax decode: (n, T) uint8 note index per row, computed on the device without materialising the
-        (n, T, D) probability tensor on the host (replaces decoder.predict + sample_vector 'argmax')."""
-        return self._run(x, batch_size, want_probs=False)[1]
+    # ---- 'choice' decode on the device ---------------------------------------------------------------------
+    sample_settings = None      # where temperature / number_of_tries / cutoff_sample_threshold come from (a settings module, namespace
+                                # or dict, read like packers._g does); None = the defaults of config.build_settings()
+
+    def _sample_spec(self, n, sample_method, temperature, seed, uniforms, heads):
+        """arguments of Engine.decode(sample=...) for ``n`` windows, or None for 'argmax'"""
+        from . import packers, sampling
+        if sample_method == "argmax":
+            if uniforms is not None or seed is not None or temperature is not None:
+                raise ValueError("temperature / seed / uniforms belong to sample_method='choice'")
+            return None
+        if sample_method != "choice":
+            raise ValueError("unknown sample_method %r" % (sample_method,))
+        s = self.sample_settings
+        if s is None:
+            from .config import build_settings
+            s = build_settings()
+        tries = int(packers._g(s, "number_of_tries"))
+        if not 1 <= tries <= sampling.MAX_TRIES:
+            raise NotImplementedError("number_of_tries = %d: the device sampler draws 1..%d times per row" % (tries, sampling.MAX_TRIES))
+        tau = float(packers._g(s, "temperature") if temperature is None else temperature)
+        if not tau > 0:
+            raise ValueError("temperature must be > 0")
+        if seed is None:        # a key stream of its own (NOT _Shared.rng: that one feeds the epsilon draws)
+            rng = getattr(self._s, "_choice_rng", None)
+            if rng is None:
+                rng = self._s._choice_rng = np.random.default_rng([int(self._s.seed), 0x63686F69])
+            seed = int(rng.integers(0, 1 << 63))
+        us = {}
+        if uniforms is not None:
+            if not isinstance(uniforms, dict):
+                uniforms = {"notes": uniforms}
+            for name, u in uniforms.items():
+                if name not in heads:
+                    raise ValueError("uniforms for %r: the model's softmax heads are %r" % (name, sorted(heads)))
+                u = sampling.as_f32_uniforms(u)
+                if u.ndim == 2:
+                    u = u[:, :, None]
+                if u.shape != (n, heads[name], tries):
+                    raise ValueError("uniforms of head %r have shape %r, expected %r (number_of_tries = %d)"
+                                     % (name, u.shape, (n, heads[name], tries), tries))
+                us[name] = u
+        return dict(temperature=tau, cutoff=float(packers._g(s, "cutoff_sample_threshold")), tries=tries, seed=int(seed), uniforms=us)
+
+    def _softmax_heads(self):
+        sp = self._s.spec
+        return {k: T for k, T in (("notes", sp.T), ("instr", sp.V), ("held", sp.T), ("next", sp.T)) if k in self._s.head_names()}
+
+    def predict_note_indices(self, x, batch_size=32, sample_method="argmax", temperature=None, seed=None, uniforms=None):
+        """Fused decode: (n, T) uint8 note index per row, computed on the device without materialising the (n, T, D) probability
+        tensor on the host (replaces decoder.predict + sample_vector).  'argmax' (default): the first maximum.  'choice': one
+        draw per row from the tempered distribution, np.random.choice's rule (reference vae_definition.py:1048-1067);
+        ``temperature`` None = the settings' value (number_of_tries and cutoff_sample_threshold come from there too:
+        ``decoder.sample_settings``); ``uniforms`` (n, T) or (n, T, number_of_tries) in [0, 1): the caller's random numbers in the
+        caller's order; else they are generated on the device from ``seed`` (None: drawn from a generator of this model, seeded
+        by ``create(seed=...)``) - the result for a window depends on the seed and the window's index only."""
+        n = np.asarray(self._unpack(x)["z"]).shape[0]
+        sample = self._sample_spec(n, sample_method, temperature, seed, uniforms, self._softmax_heads())
+        return self._run(x, batch_size, want_probs=False, sample=sample)[1]
+
+    def predict_indices(self, x, batch_size=32, sample_method="argmax", temperature=None, seed=None, uniforms=None):
+        """The decoded index of EVERY softmax head - dict 'notes' (n, T), 'instr' (n, max_voices), 'held' (n, T), 'next' (n, T)
+        uint8, as far as the model has them - plus 'velocity' (n, T) float32: what packers.process_decoder_indices needs, without
+        a probability tensor reaching the host.  Arguments as predict_note_indices; ``uniforms``: dict head -> array."""
+        n = np.asarray(self._unpack(x)["z"]).shape[0]
+        sample = self._sample_spec(n, sample_method, temperature, seed, uniforms, self._softmax_heads())
+        return self._run(x, batch_size, want_probs=False, sample=sample, all_heads=True)[2]
 
 
 class Autoencoder(_ModelView):

@@ -295,6 +295,20 @@ def head(kind, dtype, R, H, N, hs, wt, bias, *, target_idx=None, target_val=None
     hl.check(hl.load().mvae_head(a, _stream()), "mvae_head")
 
 
+def head_sample(dtype, R, H, N, hs, wt, bias, out, *, uniforms=None, u_stride=0, ctl=None, seed=0, window0=0, temperature=1.0,
+                cutoff=0.0, tries=1, b_stride=0, b_valid=0, T=0, row0=0, head_id=0):
+    """'choice' decode of a softmax head (mvae_head_sample): out (R,) uint8 = one draw per row from softmax(logits / temperature).
+    ``uniforms`` (R, u_stride) f32 or None = Philox in the kernel; ``ctl``: the 8-word device control block that then carries seed,
+    first window, temperature, cutoff and tries (sampling.control_words) - else they are the keyword values."""
+    host = hl.SampleCtl(int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF, int(window0) & 0xFFFFFFFF,
+                        (int(window0) >> 32) & 0xFFFFFFFF, float(temperature), float(cutoff), int(tries), 0)
+    a = hl.HeadSampleArgs(dtype, R, H, N, hs.data_ptr(), _p(wt), _p(bias), _pv(uniforms), _pv(ctl), _pv(out), b_stride, b_valid,
+                          int(T), int(row0), int(head_id), int(u_stride), host)
+    _tag(a, "b_valid", b_valid)
+    _note_fields(0, [a])
+    hl.check(hl.load().mvae_head_sample(a, _stream()), "mvae_head_sample")
+
+
 def latent_fwd(B, Z, C, beta, prior_mean, prior_std, inv_batch, mu, logvar, eps, z, scalars, *, style_target=None,
                style_row_weight=None, style_probs=None, ldz=0):
     a = hl.LatentFwdArgs(B, Z, C, beta, prior_mean, prior_std, inv_batch, _p(mu), _p(logvar), _p(eps),

@@ -328,6 +328,46 @@ def process_decoder_outputs(s, decoder_outputs, sample_method):
     return Y, I, V, D, N
 
 
+def process_decoder_indices(s, indices):
+    """``process_decoder_outputs`` from decoded INDICES (``decoder.predict_indices``: dict 'notes' (n, T), and as far as the model
+    has the heads 'instr' (n, max_voices), 'velocity' (n, T) float, 'held' (n, T), 'next' (n, T)) -> (Y, I, V, D, N): exactly what
+    process_decoder_outputs(s, <one-hot rows of those indices>, 'argmax') returns - silent column, velocity rules, the defaults for
+    absent heads - without the (n, T, D) tensors.  The index of a head may have been drawn by any sample method.
+    The reference reads element 1 of the output list as the instrument head whenever ANY meta head is on (:1131-1225); with
+    ``meta_instrument`` off and another meta head on that decodes the wrong head, and is refused here."""
+    T = _g(s, "output_length")
+    metas = [f for f in ("meta_velocity", "meta_held_notes", "meta_next_notes") if _g(s, f)]
+    if metas and not _g(s, "meta_instrument"):
+        raise NotImplementedError("process_decoder_indices with %s on and meta_instrument off: the reference decodes that "
+                                  "head as the instrument head" % metas[0])
+    Y = notes_from_indices(s, np.asarray(indices["notes"]).astype(np.int64), _g(s, "output_dim"))
+    I = V = D = N = None
+    if _g(s, "meta_instrument"):
+        idx = np.asarray(indices["instr"]).astype(np.int64)
+        I = np.zeros(idx.shape + (_g(s, "meta_instrument_dim"),))
+        np.put_along_axis(I, idx[..., None], 1, axis=-1)
+    if _g(s, "meta_velocity"):
+        V = apply_velocity_rules(s, Y, np.asarray(indices["velocity"], np.float64).reshape(-1)[:Y.shape[0]])
+    if _g(s, "meta_held_notes"):
+        D = np.asarray(np.asarray(indices["held"]).ravel(), dtype=int)
+    if _g(s, "meta_next_notes"):
+        N = notes_from_indices(s, np.asarray(indices["next"]).astype(np.int64), _g(s, "output_dim"))
+    L = Y.shape[0]
+    thr = _g(s, "velocity_threshold_such_that_it_is_a_played_note")
+    if I is None:
+        I = np.zeros((L // T, _g(s, "max_voices"), _g(s, "meta_instrument_dim")))
+        I[:, 0] = 1
+    if V is None:
+        V = np.ones((L,)) * (thr + (1.0 - thr) * 0.5)
+    if D is None:
+        D = np.ones((L,))
+        if _g(s, "meta_velocity"):
+            D[V > thr] = 0
+    if N is None:
+        N = np.zeros(Y.shape)
+    return Y, I, V, D, N
+
+
 def process_autoencoder_outputs(s, autoencoder_outputs, sample_method):
     """reference vae_definition.py:1234-1235."""
     return process_decoder_outputs(s, autoencoder_outputs, sample_method)

@@ -33,7 +33,7 @@ RECORDABLE = (
     "mvae_make_table", "mvae_transpose_convert", "mvae_adam_step", "mvae_adam_step_dev", "mvae_rmsprop_step",
     "mvae_scalars_accumulate", "mvae_copy2d_f32", "mvae_history_from_latent", "mvae_signature_head_fwd",
     "mvae_signature_head_bwd", "mvae_softmax_bwd_add", "mvae_bi_concat", "mvae_add_time_reversed", "mvae_event_record",
-    "mvae_stream_wait_event")
+    "mvae_stream_wait_event", "mvae_head_sample")
 _M64 = (1 << 64) - 1
 _active = None          # the Recorder noting calls right now (one at a time: the engine's enqueue is single-threaded)
 

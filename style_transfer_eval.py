@@ -7,7 +7,7 @@ given (z', history), so the decoder runs them as ONE batch (BASELINE configs[4])
 Synthetic songs (the reference reads MIDI folders); the VAE and the pitch classifier are trained here for a few epochs first, so
 the printed numbers only show the pipeline working - not the paper's results.
 
-    python style_transfer_eval.py [--epochs 3] [--songs 8]
+    python style_transfer_eval.py [--epochs 3] [--songs 8] [--sample-method argmax|choice]
 """
 import argparse
 import time
@@ -26,6 +26,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--epochs", type=int, default=3)
     ap.add_argument("--songs", type=int, default=8)
+    ap.add_argument("--sample-method", choices=("argmax", "choice"), default="argmax",
+                    help="'choice': the reference's default decode (settings.temperature, :1048-1067), drawn on the device")
     args = ap.parse_args()
     s = vars(settings)
     nc, bs = s["num_classes"], s["batch_size"]
@@ -34,6 +36,7 @@ def main():
         n = sg["X"].shape[0]
         sg.update(Y=sg["X"], D=np.zeros(sg["V"].shape), S=np.zeros((n, s["signature_vector_length"])))
     model = VAE().create(**create_kwargs(s))
+    model.decoder.sample_settings = s
     clf = StyleClassifier("pitch", input_dim=s["input_dim"], num_classes=nc, learning_rate=2e-4)
     for e in range(args.epochs):
         hs = []
@@ -55,7 +58,7 @@ def main():
         z2[:, C], z2[:, target] = z[:, target], z[:, C]                                                     # :2471-2478
         for name, zz in (("kept", z), ("switched", z2)):
             dec_in = vae_definition.prepare_decoder_input(zz, C, sg["S"], None)    # history = previous window's (switched) z, :2481
-            idx = model.decoder.predict_note_indices(dec_in, batch_size=max(bs, n))                         # :2482-2483, fused
+            idx = model.decoder.predict_note_indices(dec_in, batch_size=max(bs, n), sample_method=args.sample_method)    # :2482-2483, fused
             pred = np.argmax(clf.predict(idx, batch_size=bs), axis=1)
             if name == "kept":
                 kept += int(np.sum(pred == C))

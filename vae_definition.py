@@ -4,11 +4,21 @@ to the flat ``settings`` namespace at call time exactly like the reference's sta
 import midi_vae_amd  # noqa: F401
 import settings as _settings
 from midi_vae_amd import packers as _pk
-from midi_vae_amd.model import VAE  # noqa: F401
+from midi_vae_amd.model import VAE as _VAE
 
 
 def _s():
     return vars(_settings)
+
+
+class VAE(_VAE):
+    """the engine's VAE bound to ``settings`` like everything else here: a 'choice' decode on the device (decoder.predict_note_indices /
+    predict_indices) reads temperature, number_of_tries and cutoff_sample_threshold from the module at call time"""
+
+    def create(self, *args, **kw):
+        super().create(*args, **kw)
+        self.decoder.sample_settings = _settings
+        return self
 
 
 def prepare_encoder_input_list(X, I, V, D):
@@ -41,6 +51,10 @@ def sample_held_notes_prediction(D, sample_method):
 
 def process_decoder_outputs(decoder_outputs, sample_method):
     return _pk.process_decoder_outputs(_s(), decoder_outputs, sample_method)
+
+
+def process_decoder_indices(indices):
+    return _pk.process_decoder_indices(_s(), indices)
 
 
 def process_autoencoder_outputs(autoencoder_outputs, sample_method):
