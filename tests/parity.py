@@ -59,6 +59,15 @@ rtol |want| + floor * RMS(want) (``ELEMWISE_F32`` / ``assert_elementwise``): num
 (tests/latent_ref.py in float32 at every chain case, the tanh of the float32 accumulation models; test_parity_gemm_cpu.py) is
 within 1.85 x (1e-5 |want| + 1e-5 RMS) - d(logvar) of a row with eps = 60, 0.45 x otherwise; x 4: rtol = floor = 8e-5.
 The margins measured on the MI355X against all of these are in profiles/r09_op_parity_margins.txt.
+
+The saturated and clipped regime.  The default problems sit in the smooth interior of every non-linearity (no gate clipped, no
+target probability near a clip of the cross-entropy).  ``rnn_saturated_problem`` (inputs of standard deviation 2, planted rows at
++-60), ``softmax_head_clipped_problem`` (target probabilities below 1e-9 / above 1 - 1e-9, one-hot and two-hot) and
+``sigmoid_head_saturated_problem`` (logits +-100 and exactly 0) sit on the kinks, with the SAME bounds: the bf16 rounding model
+stays below 0.4 x every bound on them (test_parity_cpu.py), a derivative of 0.2 at a clipped gate, unclipped gates, a NaN from
+tanh, a leaking or dropped gradient of a clipped target and an unclipped loss all fail.  Where Keras' derivative is zero the
+kernels must return exactly zero (``assert_clipped_gates_have_no_gradient``, all-zero blocks of ``assert_parity``).  Margins on
+the MI355X: profiles/r10_saturation_margins.txt.
 """
 import os
 
@@ -142,6 +151,8 @@ def parity_ratios(got, want, dtype, blocks, values=False):
 def assert_parity(got, want, dtype, blocks, what, values=False):
     """fail with the block's name and the worst ratio; return the ratios (for calibration)"""
     r = parity_ratios(got, want, dtype, blocks, values)
+    _record("parity:" + ("bf16" if dtype == BF16 else "f32") + (":values" if values else ""), what, elem=r["elem"], norm=r["norm"],
+            norm_rel=r["norm_rel"])
     assert r["elem"] <= 1.0, "%s, %s: elementwise error %.3g x the bound" % (what, r["elem_at"], r["elem"])
     assert r["norm"] <= 1.0, "%s, %s: normwise error %.3g x the bound (%.2e)" % (what, r["norm_at"], r["norm"], r["norm_rel"])
     return r
@@ -150,6 +161,7 @@ def assert_parity(got, want, dtype, blocks, what, values=False):
 def assert_rel(got, want, rtol, what):
     """a scalar within rtol of the oracle's; returns |err| / (rtol |want|)"""
     r = float(_ratio(np.abs(np.float64(got) - np.float64(want)), rtol * np.abs(np.float64(want))))
+    _record("rel", what, ratio=r)
     assert r <= 1.0, "%s: %.9g vs %.9g (%.3g x the bound %.0e)" % (what, got, want, r, rtol)
     return r
 
@@ -180,6 +192,96 @@ def rnn_backward_problem(cellname, H, T, B, ext, rnd):
     return U, hs_o, cs_o, acts_o, dext, dlast
 
 
+# ---- the saturated regime: clipped hard-sigmoid gates, tanh far out, a cell state past the range of e^{2c} ------------------
+SAT_STD, SAT_BIG = 2.0, 60.0       # spread of the pre-activation inputs; the planted rows' value (exact in bf16)
+
+
+def plant_saturated_rows(x):
+    """x (..., B, GH), in place: batch row 1 = +60, row 2 = -60, row 3 = +60 / -60 alternating by column (only when B > 3).
+    GH / G is even, so a unit's gates share their sign: an LSTM unit of row 1 has i = f = o = g = 1 and its cell state grows
+    by one every step; a unit of row 2 has i = f = o = 0 and c = h = 0."""
+    B, GH = x.shape[-2:]
+    if B > 3:
+        x[..., 1, :], x[..., 2, :] = SAT_BIG, -SAT_BIG
+        x[..., 3, :] = np.where(np.arange(GH) % 2 == 0, SAT_BIG, -SAT_BIG)
+    return x
+
+
+def saturated_seed(H, T, B):
+    """one seed per saturated shape, the same for the GPU tests and the CPU model (test_parity_cpu.py)"""
+    return 7 + H + 3 * T + B
+
+
+class Problem(dict):
+    """a dict whose keys read as attributes"""
+    __getattr__ = dict.__getitem__
+
+
+def rnn_saturated_problem(cellname, H, T, B, seed, rnd=None, xmode="dense"):
+    """``rnn_problem``'s U, h0, c0 with pre-activation inputs of standard deviation 2 (hard_sigmoid clips beyond +-2.5) and the
+    planted rows of ``plant_saturated_rows``.  xmode "dense": xp (T, B, GH); "index": a table of 7 random rows and the three
+    planted ones (rows 7, 8, 9), gathered by idx (T, B); "const": one xp0 (B, GH) for every step.  ``rnd`` rounds what the kernel
+    is handed in its storage type.  Returns the forward inputs, the oracle's forward sequences on them (hs, cs, acts: float64,
+    unrounded) and what BPTT needs: those sequences rounded (hs_r, cs_r, acts_r), an upstream gradient per step (dext, rounded)
+    and one at the final state (dlast), at the scales of ``rnn_backward_problem``."""
+    rnd = rnd or (lambda a: a)
+    rng, G, U, W, b, h0, c0 = rnn_problem(cellname, H, T, B, seed)
+    GH = G * H
+    c0 = c0 if cellname == "LSTM" else None
+    pb = Problem(U=U, h0=h0, c0=c0, G=G, idx=None, table=None, xp0=None)
+    if xmode == "dense":
+        pb.xp = rnd(plant_saturated_rows(rng.standard_normal((T, B, GH)) * SAT_STD))
+    elif xmode == "index":
+        pb.table = rnd(np.concatenate([rng.standard_normal((7, GH)) * SAT_STD, plant_saturated_rows(np.zeros((4, GH)))[1:]]))
+        pb.idx = rng.integers(0, 7, (T, B))
+        if B > 3:
+            pb.idx[:, 1], pb.idx[:, 2], pb.idx[:, 3] = 7, 8, 9
+        pb.xp = pb.table[pb.idx]
+    else:
+        assert xmode == "const", xmode
+        pb.xp0 = rnd(plant_saturated_rows(rng.standard_normal((B, GH)) * SAT_STD))
+        pb.xp = np.broadcast_to(pb.xp0[None], (T, B, GH)).copy()
+    pb.hs, pb.cs, pb.acts = vo.rnn_forward(cellname, pb.xp, U, h0, c0)
+    pb.hs_r, pb.acts_r, pb.cs_r = rnd(pb.hs), rnd(pb.acts), (rnd(pb.cs) if pb.cs is not None else None)
+    pb.dext = rnd(rng.standard_normal((T, B, H)) * 0.1)
+    pb.dlast = rng.standard_normal((B, H)) * 0.1
+    return pb
+
+
+def hard_sigmoid_gates(cellname, acts):
+    """the hard-sigmoid gates of acts / da (T, B, G*H) as (T, B, n, H): LSTM i, f, o; GRU z, r; SimpleRNN has none"""
+    T, B, GH = acts.shape
+    G = len(GATE_NAMES[cellname])
+    a = acts.reshape(T, B, G, GH // G)
+    return a[:, :, {"LSTM": [0, 1, 3], "GRU": [0, 1], "SimpleRNN": []}[cellname]]
+
+
+def clipped_share(cellname, acts):
+    """(share of hard-sigmoid gate values that are exactly 0, share that are exactly 1)"""
+    g = hard_sigmoid_gates(cellname, acts)
+    return float(np.mean(g == 0.0)), float(np.mean(g == 1.0))
+
+
+def assert_clipped_gates_have_no_gradient(cellname, acts, da, what=""):
+    """wherever the SAVED gate value a BPTT kernel was handed is exactly 0 or 1, its pre-activation gradient is exactly zero
+    (Keras: the gradient of clip() outside the range); returns the number of such elements"""
+    g, d = hard_sigmoid_gates(cellname, np.asarray(acts, np.float64)), hard_sigmoid_gates(cellname, np.asarray(da, np.float64))
+    clipped = (g == 0.0) | (g == 1.0)
+    bad = clipped & (d != 0.0)
+    assert not bad.any(), "%s: %d of %d clipped gates carry a gradient, first at (t, b, gate, unit) = %s: %r" % (
+        what, bad.sum(), clipped.sum(), tuple(np.argwhere(bad)[0]), d[bad][0])
+    return int(clipped.sum())
+
+
+# (H, B) of the saturated forward cases (T = 9) and BPTT cases (T = 8): a ragged generic shape, a ragged and a whole-tile batch at
+# the resident kernels' H = 256; the wider generic kernels (test_hidden_sizes_gpu.py); the long LSTM window whose cell state leaves
+# the range of e^{2c}
+SAT_FWD_SHAPES = [(64, 5), (256, 21), (256, 32)]
+SAT_BWD_SHAPES = [(64, 5), (256, 19), (256, 32)]
+SAT_WIDE_SHAPES = [(384, 21), (512, 16)]
+SAT_T_FWD, SAT_T_BWD, SAT_LONG = 9, 8, (256, 64, 16)           # SAT_LONG: (H, T, B)
+
+
 def softmax_head_problem(N, H, R, seed, two_hot=False):
     """hs (R, H), W (H, N) (logits of the same spread at every H), bias, target index per row (row 5: all-zero target), row
     weights ~ 1/R; ``two_hot``: a second target index per row (255 = none on about a third of the rows and on row 5), never
@@ -208,6 +310,125 @@ def softmax_head_oracle(hs, Wq, bias, tgt, rw, grad_scale, tgt2=None):
         ok = t < N
         y[np.nonzero(ok)[0], t[ok]] = 1
     return p, np.sum(rw * vo._cce(p, y)), grad_scale * rw[:, None] * vo._cce_grad_logits(p, y), y
+
+
+SHARED_LOGIT, SHARED_DROP = 10.0, 36.0
+CE_FAR, CE_NEAR = 1e-9, 1e-6      # a target probability is beyond a clip by a factor 100, or inside it by a factor 10
+
+
+def ce_bands(hs, Wq, bias, tgt, tgt2=None):
+    """float64 target probabilities of a softmax head problem, on the rounded operands the oracle gets: every one must be below
+    1e-9, above 1 - 1e-9 or inside [1e-6, 1 - 1e-6], so that no f32 evaluation (relative error ~1e-6) can land on the other side
+    of Keras' clip at 1e-7.  Returns boolean (R, 2) arrays low, high, inside (all False where there is no target)."""
+    z = hs @ Wq + bias
+    z = z - z.max(1, keepdims=True)
+    e = np.exp(z)
+    p = e / e.sum(1, keepdims=True)
+    N = Wq.shape[1]
+    q = np.stack([np.delete(e, c, 1).sum(1) for c in range(N)], 1) / e.sum(1, keepdims=True)     # 1 - p without cancellation
+    R = hs.shape[0]
+    low, high, inside = (np.zeros((R, 2), bool) for _ in range(3))
+    for s, t in enumerate((tgt, tgt2)):
+        if t is None:
+            continue
+        rows = np.nonzero(np.asarray(t) < N)[0]
+        pt, qt = p[rows, np.asarray(t)[rows]], q[rows, np.asarray(t)[rows]]
+        low[rows, s], high[rows, s] = pt < CE_FAR, qt < CE_FAR
+        inside[rows, s] = (pt >= CE_NEAR) & (qt >= CE_NEAR)
+        bad = ~(low[rows, s] | high[rows, s] | inside[rows, s])
+        assert not bad.any(), "rows %s: target probabilities %s are too close to a clip of the cross-entropy" % (rows[bad], pt[bad])
+    return low, high, inside
+
+
+def softmax_head_clipped_problem(N, H, R, seed, two_hot=False, rnd=None, s=12.0):
+    """``softmax_head_problem`` with rows whose target probabilities lie beyond Keras' clip [1e-7, 1 - 1e-7] (no gradient from such a
+    target, each target of a two-hot row on its own; -log(1e-7) as its loss).  hs[row] = s W[:, j] lifts column j by more than 30
+    in logit over every other column ("high" = j, "low" = any other); hs[row] = a W[:, j] + b W[:, m] + c W[:, low] with logits of
+    10, 10 and -26 at those columns leaves j and m "inside" and column ``low`` 36 below them.  j = N - 1 (the last column of the
+    last tile), m = N // 2, low = column 0.  Planted rows: 0 high, 1 low; two-hot: 2 (low, inside), 3 (inside, low), 4 (low, high), 6 (high, low), 7 (low, low), R - 3 (low, inside); one-hot:
+    6 high, 7 low; R - 2: low (one-hot in both - a fully clipped row in the last, partial 16-row tile).  Rows 6 and 7 are padding
+    positions under b_stride = 8, b_valid = 5; row 5 keeps its all-zero target.  ``rnd`` rounds to the kernel's storage type: hs comes
+    back rounded, W does not (the device converts it), and the conditions of ``ce_bands`` are asserted on rnd(hs), rnd(W).
+    Returns softmax_head_problem's tuple and a dict case name -> row."""
+    rnd = rnd or (lambda a: a)
+    assert N >= 3 and R >= 24
+    rng, hs, W, bias, tgt, rw, tgt2 = softmax_head_problem(N, H, R, seed, two_hot)
+    Wq = rnd(W)
+    j, m, lo = N - 1, N // 2, 0
+    dominant = s * Wq[:, j]
+    # the "inside" rows keep their logits SMALL: an f32 logit near 70 carries rounding errors of several 1e-6 (half an ulp is 3.8e-6
+    # there), which is the relative error of a probability that is not 0 or 1 - more than the f32 bound on forward values allows a
+    # correct kernel.  So columns j and m sit at a logit of 10 and the low column is pushed DOWN to -26 (test_parity_cpu.py runs a
+    # float32 model of a correct head on these problems: it must stay below half of every bound)
+    trio = Wq[:, [j, m, lo]]
+    shared = trio @ np.linalg.solve(trio.T @ trio, np.array([SHARED_LOGIT, SHARED_LOGIT, SHARED_LOGIT - SHARED_DROP]))
+    NONE = 255
+    if two_hot:
+        plan = {"high": (0, dominant, j, NONE), "low": (1, dominant, lo, NONE), "low_inside": (2, shared, lo, j),
+                "inside_low": (3, shared, j, lo), "low_high": (4, dominant, lo, j), "high_low": (6, dominant, j, lo),
+                "low_low": (7, dominant, lo, m), "low_inside_last_tile": (R - 3, shared, lo, m),
+                "low_last_tile": (R - 2, dominant, lo, NONE)}
+    else:
+        plan = {"high": (0, dominant, j, NONE), "low": (1, dominant, lo, NONE), "high_padding": (6, dominant, j, NONE),
+                "low_padding": (7, dominant, lo, NONE), "low_last_tile": (R - 2, dominant, lo, NONE)}
+    for row, h, t1, t2 in plan.values():
+        hs[row], tgt[row] = h, t1
+        if two_hot:
+            tgt2[row] = t2
+    hs = rnd(hs)
+    low, high, inside = ce_bands(hs, Wq, bias, tgt, tgt2)
+    for name, (row, _, t1, t2) in plan.items():              # every planted target is in the band its name says
+        kinds = name.replace("_last_tile", "").replace("_padding", "").split("_")
+        for slot, kind in enumerate(kinds):
+            assert dict(low=low, high=high, inside=inside)[kind][row, slot], (name, row, slot)
+    assert tgt[5] == NONE and (tgt2 is None or tgt2[5] == NONE)
+    return rng, hs, W, bias, tgt, rw, tgt2, {name: v[0] for name, v in plan.items()}
+
+
+# (N, H, R, two_hot) -> seed of every clipped head case the GPU tests run: the first seed >= N at which the float64 oracle meets the
+# conditions of ``ce_bands`` on unrounded, f32-rounded and bf16-rounded operands (found on the CPU; test_parity_cpu.py re-asserts)
+CLIPPED_HEAD_SEEDS = {(3, 64, 40, False): 3, (3, 64, 40, True): 3, (3, 64, 48, False): 3, (3, 64, 48, True): 3, (3, 256, 48, False): 3,
+                      (3, 256, 48, True): 3, (61, 64, 40, False): 61, (61, 64, 40, True): 62, (61, 64, 48, False): 61,
+                      (61, 64, 48, True): 61, (61, 256, 48, False): 61, (61, 256, 48, True): 61, (145, 64, 40, False): 145,
+                      (145, 64, 40, True): 145, (145, 64, 48, False): 146, (145, 64, 48, True): 146, (145, 256, 48, False): 146,
+                      (145, 256, 48, True): 145}
+
+
+def retarget_padding_rows(hs, Wq, bias, tgt, tgt2, counted, keep):
+    """in place, as test_ops_gpu._softmax_head_case does: a padding row (not ``counted``) gets its own argmax as its only target - a
+    hit if it were counted - except the planted rows ``keep``"""
+    rows = np.setdiff1d(np.nonzero(~counted)[0], list(keep))
+    tgt[rows] = np.argmax(hs[rows] @ Wq + bias, 1)
+    if tgt2 is not None:
+        tgt2[rows] = 255
+    return rows
+
+
+def fully_clipped_rows(low, high, inside):
+    """rows of a softmax head problem with a target and none inside the clip range: d(logits) and dhs must be exactly zero"""
+    return np.nonzero((low | high).any(1) & ~inside.any(1))[0]
+
+
+def sigmoid_head_saturated_problem(R, H, seed, rnd=None):
+    """test_sigmoid_head's problem with zero bias and planted rows: logits of +100 (rows 0, 1: targets 1, 0) and -100 (rows 2, 3:
+    targets 0, 1) - exp(-100) is below half an ulp of 1 and exp(100) above the f32 range, so pr is exactly 1 / 0 and the gradient
+    2 (pr - y) pr (1 - pr) exactly zero - and all-zero hs rows (4 and R - 1, targets 0 and 1): the logit is exactly 0, pr exactly
+    1/2, which Keras' binary accuracy rounds half-to-even to 0.  Returns hs (rounded), W (H, 1), bias, y, rw and the planted rows."""
+    rnd = rnd or (lambda a: a)
+    rng = np.random.default_rng(seed)
+    hs = rng.standard_normal((R, H))
+    W = rng.standard_normal((H, 1)) * 0.3
+    y = np.where(rng.random(R) < 0.5, 0.0, 0.5 + 0.5 * rng.random(R))
+    rw = rng.random((R,)) / R
+    Wq = rnd(W)[:, 0]
+    big = (100.0 / (Wq @ Wq)) * Wq
+    rows = dict(plus=[0, 1], minus=[2, 3], half=[4, R - 1])
+    hs[0], hs[1], hs[2], hs[3], hs[4], hs[R - 1] = big, big, -big, -big, 0.0, 0.0
+    y[[0, 1, 2, 3, 4, R - 1]] = [1.0, 0.0, 0.0, 1.0, 0.0, 1.0]
+    hs = rnd(hs)
+    z = hs @ Wq
+    assert np.all(np.abs(z[rows["plus"]] - 100.0) < 5.0) and np.all(np.abs(z[rows["minus"]] + 100.0) < 5.0) and np.all(z[rows["half"]] == 0)
+    return hs, W, np.array([0.0]), y, rw, rows
 
 
 def fused_head_problem(kind, N, H, R, seed):

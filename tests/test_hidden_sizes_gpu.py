@@ -15,6 +15,7 @@ from midi_vae_amd.model import VAE
 from midi_vae_amd.synth import make_windows, to_reference_format
 from oracle.classifier_oracle import OracleClassifier
 from oracle.vae_oracle import OracleVAE, make_cfg
+from tests import parity as par
 from tests.test_classifier_gpu import _problem as _cls_problem
 from tests.test_engine_gpu import _problem, _rel_l2, _stage
 
@@ -38,6 +39,23 @@ def test_rnn_forward_new_sizes(cellname, cell, dtype, tol, H, xmode):
 @pytest.mark.parametrize("ext", [True, False])
 def test_rnn_backward_new_sizes(cellname, cell, dtype, tol, H, ext):
     ops_t._rnn_backward_case(cellname, cell, dtype, tol, H, RAGGED_B[H] if ext else 16, ext, T=8)
+
+
+@pytest.mark.parametrize("cellname,cell", ops_t.CELLS)
+@pytest.mark.parametrize("dtype,tol", ops_t.DTYPES)
+@pytest.mark.parametrize("xmode", ["dense", "index"])
+@pytest.mark.parametrize("H,B", par.SAT_WIDE_SHAPES)
+def test_rnn_forward_saturated_new_sizes(cellname, cell, dtype, tol, xmode, H, B):
+    """clipped gates and the planted +-60 rows (tests/parity.py rnn_saturated_problem) at the wide generic kernels"""
+    ops_t._rnn_forward_saturated_case(cellname, cell, dtype, tol, xmode, H, B, par.SAT_T_FWD)
+
+
+@pytest.mark.parametrize("cellname,cell", ops_t.CELLS)
+@pytest.mark.parametrize("dtype,tol", ops_t.DTYPES)
+@pytest.mark.parametrize("H,B", par.SAT_WIDE_SHAPES)
+@pytest.mark.parametrize("ext", [True, False])
+def test_rnn_backward_saturated_new_sizes(cellname, cell, dtype, tol, H, B, ext):
+    ops_t._rnn_backward_case(cellname, cell, dtype, tol, H, B, ext, T=par.SAT_T_BWD, saturated=True)
 
 
 # ---- engine ----------------------------------------------------------------------------------------------------------------

@@ -15,6 +15,10 @@ normwise, zero stays zero - constants from a CPU model of a correct accumulation
 once more on small-integer operands, where the result must be BIT-equal to float64 (parity.assert_bits).  The kernels of
 csrc/misc.hip and csrc/latent.hip have files of their own: test_small_ops_gpu.py, test_latent_ops_gpu.py.  Margins measured on
 the MI355X against the new bounds: profiles/r09_op_parity_margins.txt.
+Saturation: the ``*_saturated`` / ``*_clipped_rows`` / ``*_extremes`` tests run the same paths on problems that sit ON the kinks
+(tests/parity.py: clipped hard-sigmoid gates and planted +-60 rows, a cell state past the range of e^{2c}, target probabilities
+beyond both clips of the cross-entropy, sigmoid logits of +-100 and 0) with the same bounds, exact zeros where the derivative is
+zero, and the forward kernels' own buffers handed to the backward kernels; margins: profiles/r10_saturation_margins.txt.
 """
 import numpy as np
 import pytest
@@ -194,11 +198,22 @@ def test_rnn_forward(cellname, cell, dtype, tol, xmode, H, B):
         xp = np.broadcast_to(xp0[None], (T, B, GH)).copy()
         kw["xp0"] = dev(xp0, td)
     hs_o, cs_o, acts_o = vo.rnn_forward(cellname, xp, U, h0, c0 if cellname == "LSTM" else None)
+    _rnn_forward_run(cellname, cell, dtype, tol, xmode, T, B, H, U, h0, c0, kw, (hs_o, cs_o, acts_o))
 
+
+def _rnn_forward_run(cellname, cell, dtype, tol, xmode, T, B, H, U, h0, c0, kw, oracle, keep_device=False):
+    """the forward kernel of every sequence layout the shape takes, on the inputs ``kw`` (row-major device tensors), against the
+    oracle's (hs, cs, acts): ``close`` and the parity bounds.  Returns one dict per layout: the outputs as row-major float64 and the
+    worst ratio to the bounds per output; ``keep_device``: also the kernel's own buffers, untouched and in their layout."""
+    hs_o, cs_o, acts_o = oracle
+    GH = vo.GATES[cellname] * H
+    td = ops.torch_dtype(dtype)
+    kw = dict(kw)
     up = ops.pack_recurrent(dev(U), cell, dtype, 0)
     res = resident(H, B, dtype, cell)
     if res and "xp" in kw:
         kw["xp"] = tile16(kw["xp"], T * B, GH, True)
+    runs = []
     for lay in seq_layouts(res, cellname, xmode):
         hs = torch.zeros((T + 1, B, H), dtype=td, device=DEV)
         cs = torch.zeros((T + 1, B, H), dtype=td, device=DEV) if cellname == "LSTM" else None
@@ -214,6 +229,7 @@ def test_rnn_forward(cellname, cell, dtype, tol, xmode, H, B):
         ops.rnn_fwd(cell, dtype, T, B, H, up, h0=dev(h0), c0=dev(c0) if cellname == "LSTM" else None, hs=hs, cs=cs,
                     acts=acts, h_last=h_last, seq_layout=lay, **kwl)
         torch.cuda.synchronize()
+        own = dict(hs=hs, cs=cs, acts=acts) if keep_device else None
         if res:
             acts = tile16(acts, T * B, GH, False, paired=pairing(lay))
             if cs is not None:
@@ -224,11 +240,14 @@ def test_rnn_forward(cellname, cell, dtype, tol, xmode, H, B):
         close(host(h_last), hs_o[-1], tol, "h_last" + what)
         if cs is not None:
             close(host(cs), cs_o, tol, "cs" + what)
-        par.assert_parity(host(hs), hs_o, dtype, par.step_blocks, "hs" + what, values=True)
-        par.assert_parity(host(acts), acts_o, dtype, par.gate_blocks(cellname), "acts" + what, values=True)
-        par.assert_parity(host(h_last), hs_o[-1], dtype, par.whole, "h_last" + what, values=True)
+        ratios = dict(hs=par.assert_parity(host(hs), hs_o, dtype, par.step_blocks, "hs" + what, values=True),
+                      acts=par.assert_parity(host(acts), acts_o, dtype, par.gate_blocks(cellname), "acts" + what, values=True),
+                      h_last=par.assert_parity(host(h_last), hs_o[-1], dtype, par.whole, "h_last" + what, values=True))
         if cs is not None:
-            par.assert_parity(host(cs), cs_o, dtype, par.step_blocks, "cs" + what, values=True)
+            ratios["cs"] = par.assert_parity(host(cs), cs_o, dtype, par.step_blocks, "cs" + what, values=True)
+        runs.append(dict(lay=lay, res=res, hs=host(hs), cs=host(cs) if cs is not None else None, acts=host(acts), h_last=host(h_last),
+                         ratios=ratios, own=own))
+    return runs
 
 
 @pytest.mark.parametrize("xmode", ["dense", "index", "const"])
@@ -334,11 +353,18 @@ def test_lstm_backward_two_waves_per_simd_experiment_keeps_parity(T, ext, monkey
     _rnn_backward_case("LSTM", hl.LSTM, hl.BF16, dict(DTYPES)[hl.BF16], 256, 32, ext, T=T)
 
 
-def _rnn_backward_case(cellname, cell, dtype, tol, H, B, ext, T):
+def _rnn_backward_case(cellname, cell, dtype, tol, H, B, ext, T, saturated=False):
+    """``saturated``: the problem of par.rnn_saturated_problem (clipped gates, planted rows) instead of par.rnn_backward_problem,
+    and beyond the same checks: a gate whose SAVED value is exactly 0 or 1 has a gradient of exactly zero, and rh = r * h exactly
+    where r is clipped"""
     GH = vo.GATES[cellname] * H
     td = ops.torch_dtype(dtype)
     rnd = (lambda a: host(dev(a, td))) if dtype == hl.BF16 else (lambda a: a)
-    U, hs_o, cs_o, acts_o, dext, dlast = par.rnn_backward_problem(cellname, H, T, B, ext, rnd)
+    if saturated:
+        pb = par.rnn_saturated_problem(cellname, H, T, B, par.saturated_seed(H, T, B), lambda a: host(dev(a, td)))
+        U, hs_o, cs_o, acts_o, dext, dlast = pb.U, pb.hs_r, pb.cs_r, pb.acts_r, (pb.dext if ext else None), pb.dlast
+    else:
+        U, hs_o, cs_o, acts_o, dext, dlast = par.rnn_backward_problem(cellname, H, T, B, ext, rnd)
     da_o, dU_o, dh0_o, dc0_o = vo.rnn_backward(cellname, hs_o, cs_o, acts_o, U, dext, dlast)
 
     ut = ops.pack_recurrent(dev(U), cell, dtype, 1)
@@ -369,6 +395,133 @@ def _rnn_backward_case(cellname, cell, dtype, tol, H, B, ext, T):
         par.assert_parity(host(dh0), dh0_o, dtype, par.whole, "dh0" + what)
         if cellname == "LSTM":
             par.assert_parity(host(dc0), dc0_o, dtype, par.whole, "dc0" + what)
+        if saturated:
+            _saturated_backward_checks(cellname, H, acts_o, hs_o, host(da), host(rh), what)
+
+
+def _saturated_backward_checks(cellname, H, acts, hs, da, rh, what):
+    """acts / hs: the saved sequences the kernel was handed (row-major float64); at least 10 % of the gates must be clipped per side"""
+    if cellname == "SimpleRNN":
+        return
+    n = par.assert_clipped_gates_have_no_gradient(cellname, acts, da, "da" + what)
+    lo, hi = par.clipped_share(cellname, acts)
+    assert lo >= 0.10 and hi >= 0.10 and n > 0, (lo, hi)
+    if cellname == "GRU":
+        r = acts[:, :, H:2 * H]
+        clipped = (r == 0.0) | (r == 1.0)
+        assert np.array_equal(rh[clipped], (r * hs[:-1])[clipped]), "rh at a clipped reset gate" + what
+
+
+@pytest.mark.parametrize("cellname,cell", CELLS)
+@pytest.mark.parametrize("dtype,tol", DTYPES)
+@pytest.mark.parametrize("xmode", ["dense", "index"])
+@pytest.mark.parametrize("H,B", par.SAT_FWD_SHAPES)
+def test_rnn_forward_saturated(cellname, cell, dtype, tol, xmode, H, B):
+    """test_rnn_forward on par.rnn_saturated_problem: pre-activation inputs of standard deviation 2 - 14 to 34 % of the hard-sigmoid
+    gate values clipped at 0 and as many at 1 - and the planted rows +60 / -60 / alternating (tanh of +-60: e^{2x} = inf in the
+    hardware form); dense input and table rows that carry the large values; every sequence layout of the shape.  (H = 384, 512:
+    test_hidden_sizes_gpu.py)"""
+    _rnn_forward_saturated_case(cellname, cell, dtype, tol, xmode, H, B, par.SAT_T_FWD)
+
+
+def _rnn_forward_saturated_case(cellname, cell, dtype, tol, xmode, H, B, T, keep_device=False):
+    td = ops.torch_dtype(dtype)
+    pb = par.rnn_saturated_problem(cellname, H, T, B, par.saturated_seed(H, T, B), lambda a: host(dev(a, td)), xmode)
+    if xmode == "dense":
+        kw = dict(xp=dev(pb.xp, td))
+    elif xmode == "index":
+        kw = dict(idx=dev(pb.idx, torch.uint8), table=dev(pb.table, td))
+    else:
+        kw = dict(xp0=dev(pb.xp0, td))
+    if cellname != "SimpleRNN":
+        lo, hi = par.clipped_share(cellname, pb.acts)
+        assert lo >= 0.10 and hi >= 0.10, (lo, hi)
+    runs = _rnn_forward_run(cellname, cell, dtype, tol, xmode, T, B, H, pb.U, pb.h0, pb.c0, kw, (pb.hs, pb.cs, pb.acts),
+                            keep_device=keep_device)
+    for run in runs:
+        for a in (run["hs"], run["cs"], run["acts"], run["h_last"]):
+            assert a is None or np.all(np.isfinite(a))
+    return pb, runs
+
+
+@pytest.mark.parametrize("dtype,tol", DTYPES)
+@pytest.mark.parametrize("xmode", ["dense", "const"])
+def test_lstm_forward_cell_state_beyond_the_range_of_exp(dtype, tol, xmode):
+    """T = 64 with the forget gate of the planted rows pinned at 1: their cell state grows by one per step to 64.8, and e^{2c}
+    leaves the f32 range at c = 44.4 - tanh_fast then rests on rcp(inf) = 0.  bf16 on both resident layouts, f32 on the generic
+    kernel.  Everything stays finite and within the bounds, and the planted rows' h is EXACTLY the oracle's (cast to the storage
+    type) wherever that is decided beyond any rounding: units whose gates are all clipped at 0 (c = h = 0), and units with
+    |c| > 12, where 1 - tanh(c) < 8e-11 - far below half an ulp of 1 in f32 - and o = 1."""
+    H, T, B = par.SAT_LONG
+    pb, runs = _rnn_forward_saturated_case("LSTM", hl.LSTM, dtype, tol, xmode, H, B, T)
+    assert np.abs(pb.cs).max() > 45
+    assert [r["lay"] for r in runs] == ([hl.TILE16, hl.TILE16P] if dtype == hl.BF16 else [hl.ROWMAJOR])
+    want = par.cast(pb.hs[:, 1:4], "bf16" if dtype == hl.BF16 else "f32")
+    decided = (pb.hs[:, 1:4] == 0.0) | (np.abs(pb.cs[:, 1:4]) > 12.0)
+    assert decided.mean() > 0.5 and np.all(np.isin(want[decided], (0.0, 1.0, -1.0)))
+    for run in runs:
+        assert np.array_equal(run["hs"][:, 1:4][decided], want[decided]), "planted rows (layout %d)" % run["lay"]
+
+
+@pytest.mark.parametrize("cellname,cell", CELLS)
+@pytest.mark.parametrize("dtype,tol", DTYPES)
+@pytest.mark.parametrize("H,B", par.SAT_BWD_SHAPES)
+@pytest.mark.parametrize("ext", [True, False])
+def test_rnn_backward_saturated(cellname, cell, dtype, tol, H, B, ext):
+    """BPTT on the saturated problem's sequences (the oracle's, rounded to the storage type): the zero branch of every
+    hard-sigmoid derivative.  (H = 384, 512: test_hidden_sizes_gpu.py)"""
+    _rnn_backward_case(cellname, cell, dtype, tol, H, B, ext, T=par.SAT_T_BWD, saturated=True)
+
+
+@pytest.mark.parametrize("cellname,cell", [c for c in CELLS if c[0] in ("GRU", "LSTM")])
+@pytest.mark.parametrize("T,ext", [(3, True), (3, False), (7, True), (7, False), (64, True)])
+def test_rnn_backward_saturated_resident_kernels_odd_and_long(cellname, cell, T, ext):
+    """the pair-unrolled loop's tail (T = 3, 7 at B = 32) and the long window (T = 64, B = 16, an upstream gradient per step: with
+    dh_last alone the gradient decays to 3e-16 over 64 saturated steps and the rounding model itself reaches 0.8 x the bound)"""
+    _rnn_backward_case(cellname, cell, hl.BF16, dict(DTYPES)[hl.BF16], 256, 16 if T == 64 else 32, ext, T=T, saturated=True)
+
+
+@pytest.mark.parametrize("T,ext", [(7, True), (7, False), (8, True), (8, False)])
+def test_lstm_backward_two_waves_per_simd_experiment_saturated(T, ext, monkeypatch):
+    """MVAE_LSTM_BWD_W8=1 (rnn_w8.hip: its own forms of the hard-sigmoid derivative) on the saturated problem"""
+    monkeypatch.setenv("MVAE_LSTM_BWD_W8", "1")
+    _rnn_backward_case("LSTM", hl.LSTM, hl.BF16, dict(DTYPES)[hl.BF16], 256, 32, ext, T=T, saturated=True)
+
+
+@pytest.mark.parametrize("cellname,cell", [c for c in CELLS if c[0] in ("GRU", "LSTM")])
+@pytest.mark.parametrize("dtype,H,B", [(hl.BF16, 256, 32), (hl.F32, 64, 5)])
+def test_rnn_saturated_forward_hands_over_to_backward(cellname, cell, dtype, H, B):
+    """The forward kernel's OWN hs / cs / acts buffers, untouched and in their layout, go to the backward kernel of the same layout
+    (the BPTT tests above always re-layout the oracle's activations).  Compared with the oracle's BPTT on those same sequences,
+    downloaded and un-tiled: both sides see the same clipped set, so this is as well conditioned as the other BPTT cases and the
+    ordinary bounds apply - the bf16 gradient check of the saturated regime."""
+    T, tol = par.SAT_T_FWD, dict(DTYPES)[dtype]
+    GH, td = vo.GATES[cellname] * H, ops.torch_dtype(dtype)
+    pb, runs = _rnn_forward_saturated_case(cellname, cell, dtype, tol, "dense", H, B, T, keep_device=True)
+    ut = ops.pack_recurrent(dev(pb.U), cell, dtype, 1)
+    assert len(runs) == ((3 if cellname == "GRU" else 2) if dtype == hl.BF16 else 1)
+    for run in runs:
+        lay, own = run["lay"], run["own"]
+        hs, cs, acts = run["hs"], run["cs"], run["acts"]                      # what the kernel stored, row-major float64
+        da_o, _, dh0_o, dc0_o = vo.rnn_backward(cellname, hs, cs, acts, pb.U, pb.dext, pb.dlast)
+        da = torch.zeros((T, B, GH), dtype=td, device=DEV)
+        rh = torch.zeros((T, B, H), dtype=td, device=DEV)
+        dh0, dc0 = torch.zeros((B, H), device=DEV), torch.zeros((B, H), device=DEV)
+        dext_d = dev(pb.dext, td)
+        if run["res"]:
+            dext_d = tile16(dext_d, T * B, H, True)
+        ops.rnn_bwd(cell, dtype, T, B, H, ut, own["hs"], own["cs"], own["acts"], da, dhs_ext=dext_d, dh_last=dev(pb.dlast), rh=rh,
+                    dh0=dh0, dc0=dc0, seq_layout=lay)
+        torch.cuda.synchronize()
+        what = " (hand-over, layout %d)" % lay
+        close(host(da), da_o, tol, "da" + what)
+        close(host(dh0), dh0_o, tol, "dh0" + what)
+        par.assert_parity(host(da), da_o, dtype, par.gate_blocks(cellname), "da" + what)
+        par.assert_parity(host(dh0), dh0_o, dtype, par.whole, "dh0" + what)
+        if cellname == "LSTM":
+            close(host(dc0), dc0_o, tol, "dc0" + what)
+            par.assert_parity(host(dc0), dc0_o, dtype, par.whole, "dc0" + what)
+        _saturated_backward_checks(cellname, H, acts, hs, host(da), host(rh), what)
 
 
 @pytest.mark.parametrize("ta,tb", [(False, False), (False, True), (True, False), (True, True)])
@@ -1163,6 +1316,131 @@ def test_head_fused_input_gradient_refuses_h_above_256(dtype):
                  target_idx=dev(rng.integers(0, N, (R,)), torch.uint8), grad_scale=1.0, dlogits=dl, wc=wc, dhs=dhs)
     torch.cuda.synchronize()
     assert torch.all(dhs == 5.0) and torch.all(dl == 3.0)
+
+
+# ---- heads at the clips of Keras' cross-entropy and at the ends of the sigmoid -----------------------------------------------------
+@pytest.mark.parametrize("dtype,tol", [(hl.F32, 2e-5), (hl.BF16, 2e-2)])
+@pytest.mark.parametrize("N", [3, 61, 145])
+@pytest.mark.parametrize("two_hot", [False, True])
+@pytest.mark.parametrize("b_stride", [0, 8])
+def test_softmax_head_clipped_rows(dtype, tol, N, two_hot, b_stride):
+    """head_k's ``inside`` / ``inside2`` (par.softmax_head_clipped_problem): R = 40 rows - a fully clipped row in the last, partial
+    16-row tile - at 1, 4 and 10 column tiles; b_stride = 8 / b_valid = 5 puts planted rows 6 and 7 at padding positions"""
+    _softmax_head_clipped_case(dtype, tol, N, 64, 40, two_hot, b_stride, fused=False)
+
+
+@pytest.mark.parametrize("dtype,tol", [(hl.F32, 2e-5), (hl.BF16, 2e-2)])
+@pytest.mark.parametrize("N", [3, 61, 145])
+@pytest.mark.parametrize("H", [64, 256])
+@pytest.mark.parametrize("two_hot", [False, True])
+def test_head_fused_input_gradient_clipped_rows(dtype, tol, N, H, two_hot):
+    """... and through the fused dhs epilogue (R = 48: it takes whole 16-row tiles only): a fully clipped row has dhs exactly zero"""
+    _softmax_head_clipped_case(dtype, tol, N, H, 48, two_hot, 0, fused=True)
+
+
+def _softmax_head_clipped_case(dtype, tol, N, H, R, two_hot, b_stride, fused):
+    td = ops.torch_dtype(dtype)
+    rnd = lambda a: host(dev(a, td))
+    rng, hs_h, W, bias, tgt, rw, tgt2, rows = par.softmax_head_clipped_problem(N, H, R, par.CLIPPED_HEAD_SEEDS[(N, H, R, two_hot)],
+                                                                               two_hot, rnd)
+    hs = dev(hs_h, td)
+    NP = ops.head_np(N)
+    wt = torch.zeros((NP, H), dtype=td, device=DEV)
+    wc = torch.zeros((H, NP), dtype=td, device=DEV)
+    pb = ops.PrepBatch()
+    pb.transpose_convert(dev(W), wt, n_pad=NP); pb.convert_pad(dev(W), wc, NP)
+    pb.run()
+    Wq = host(wt)[:N].T
+    assert np.array_equal(host(hs), hs_h) and np.array_equal(Wq, rnd(W))
+    b_valid = 5 if b_stride else 0
+    counted = (np.arange(R) % b_stride < b_valid) if b_stride else np.ones(R, bool)
+    retargeted = par.retarget_padding_rows(host(hs), Wq, bias, tgt, tgt2, counted, [5] + list(rows.values()))    # hits, if they were counted
+    low, high, inside = par.ce_bands(host(hs), Wq, bias, tgt, tgt2)         # (on exactly what the kernel is handed)
+    clipped = par.fully_clipped_rows(low, high, inside)
+    assert len(clipped) >= (6 if two_hot else 5) and R - 2 in clipped
+    p, want_loss, want_dl, y = par.softmax_head_oracle(host(hs), Wq, bias, tgt, rw, 0.7, tgt2)
+    probs = torch.zeros((R, N), device=DEV)
+    am = torch.zeros((R,), dtype=torch.uint8, device=DEV)
+    dl = torch.full((R, NP), 3.0, dtype=td, device=DEV)
+    dhs = torch.full((R, H), 5.0, dtype=td, device=DEV) if fused else None
+    sc = torch.zeros((2,), device=DEV)
+    ops.head(0, dtype, R, H, N, hs, wt, dev(bias), target_idx=dev(tgt, torch.uint8), row_weight=dev(rw), grad_scale=0.7,
+             probs=probs, argmax=am, dlogits=dl, scalars=sc, b_stride=b_stride, b_valid=b_valid,
+             target_idx2=dev(tgt2, torch.uint8) if two_hot else None, wc=wc if fused else None, dhs=dhs)
+    torch.cuda.synchronize()
+    close(host(probs), p, tol, "probs")
+    close(host(dl)[:, :N], want_dl, tol, "dlogits")
+    assert np.all(host(dl)[:, N:] == 0)
+    close(host(sc)[0], want_loss, tol * 5, "loss")
+    assert np.array_equal(am.cpu().numpy(), np.argmax(probs.cpu().numpy(), axis=1).astype(np.uint8))
+    match = np.argmax(probs.cpu().numpy(), 1) == np.argmax(y, 1)
+    assert host(sc)[1] == np.sum(match & counted)
+    assert match[rows["high"]] and all(am.cpu().numpy()[r] == N - 1 for k, r in rows.items() if "inside" not in k)
+    if b_stride:            # rows 6 and 7 are planted AND padding: a one-hot "high" row 6 is its own argmax, and must not count
+        assert len(retargeted) >= R // 4 and np.all(match[retargeted]) and not counted[6] and not counted[7]
+        assert two_hot or (match[6] and not match[7])
+    par.assert_parity(host(probs), p, dtype, par.row_blocks, "probs", values=True)
+    par.assert_parity(host(dl)[:, :N], want_dl, dtype, par.row_blocks, "dlogits")
+    # the loss: -log(1e-7) per low target.  (The high clip moves a row's loss by 1e-7 only: no loss check can see that branch; the
+    # gradient check does - a row whose only target is above 1 - 1e-7 must come back exactly zero.)
+    par.assert_rel(host(sc)[0], want_loss, par.LOSS_RTOL, "loss")
+    assert np.all(want_dl[clipped] == 0) and np.all(host(dl)[clipped] == 0) and np.all(host(dl)[5] == 0)
+    part = np.nonzero(inside.any(1) & (low | high).any(1))[0]                   # one target clipped, the other not
+    assert len(part) == (3 if two_hot else 0) and np.all(np.abs(host(dl)[part]).max(1) > 0)
+    if fused:
+        want = host(dl) @ host(wc).T
+        got = host(tile16(dhs, R, H, False))
+        close(got, want, tol, "dhs")
+        par.assert_parity(got, want, dtype, par.row_blocks, "dhs")
+        assert np.all(got[clipped] == 0) and np.all(got[5] == 0) and np.all(np.abs(got[part]).max(1) > 0)
+
+
+@pytest.mark.parametrize("dtype,tol", [(hl.F32, 2e-5), (hl.BF16, 2e-2)])
+@pytest.mark.parametrize("fused", [False, True])
+def test_sigmoid_head_at_its_extremes(dtype, tol, fused):
+    """par.sigmoid_head_saturated_problem: logits of +-100 give pr exactly 1 / 0 and a gradient of exactly zero whatever the target
+    (float64 has sigmoid(-100) = 3.7e-44 and a gradient of 1e-45: those four rows are asserted exactly, not by the bounds); a logit
+    of exactly 0 gives pr = 1/2, which Keras' binary accuracy rounds half-to-even to 0: a hit only if the target is 0"""
+    R, H = (48, 64) if fused else (40, 64)
+    td = ops.torch_dtype(dtype)
+    hs_h, W, bias, y, rw, rows = par.sigmoid_head_saturated_problem(R, H, 2, lambda a: host(dev(a, td)))
+    hs = dev(hs_h, td)
+    wt = torch.zeros((16, H), dtype=td, device=DEV)
+    wc = torch.zeros((H, 16), dtype=td, device=DEV)
+    pb = ops.PrepBatch()
+    pb.transpose_convert(dev(W), wt, n_pad=16); pb.convert_pad(dev(W), wc, 16)
+    pb.run()
+    p = vo.sigmoid(host(hs) @ host(wt)[:1].T + bias)[:, 0]
+    want_dl = rw * 2 * (p - y) * p * (1 - p)
+    probs = torch.zeros((R,), device=DEV)
+    am = torch.full((R,), 9, dtype=torch.uint8, device=DEV)
+    dl = torch.zeros((R, 16), dtype=td, device=DEV)
+    dhs = torch.full((R, H), 5.0, dtype=td, device=DEV) if fused else None
+    sc = torch.zeros((2,), device=DEV)
+    ops.head(1, dtype, R, H, 1, hs, wt, dev(bias), target_val=dev(y), row_weight=dev(rw), grad_scale=1.0, probs=probs, argmax=am,
+             dlogits=dl, scalars=sc, wc=wc if fused else None, dhs=dhs)
+    torch.cuda.synchronize()
+    pr, g, a = host(probs), host(dl)[:, 0], am.cpu().numpy()
+    ends = rows["plus"] + rows["minus"]
+    rest = np.setdiff1d(np.arange(R), ends)
+    assert np.all(pr[rows["plus"]] == 1.0) and np.all(pr[rows["minus"]] == 0.0) and np.all(g[ends] == 0.0)
+    assert np.all(a[rows["plus"]] == 1) and np.all(a[rows["minus"]] == 0)
+    assert np.all(pr[rows["half"]] == 0.5) and np.all(a[rows["half"]] == 0) and list(y[rows["half"]]) == [0.0, 1.0]
+    close(pr, p, tol)
+    close(g, want_dl, tol)
+    close(host(sc)[0], np.sum(rw * (p - y) ** 2), tol * 5)
+    hits = np.round(probs.cpu().numpy()) == y.astype(np.float32)
+    assert host(sc)[1] == np.sum(hits) and list(hits[rows["half"]]) == [True, False] and list(hits[ends]) == [True, False, True, False]
+    par.assert_parity(pr[rest, None], p[rest, None], dtype, par.row_blocks, "probs", values=True)
+    par.assert_parity(g[rest, None], want_dl[rest, None], dtype, par.row_blocks, "dlogits")
+    assert np.all(host(dl)[:, 1:] == 0)
+    par.assert_rel(host(sc)[0], np.sum(rw * (p - y) ** 2), par.LOSS_RTOL, "loss")
+    if fused:
+        want = host(dl) @ host(wc).T
+        got = host(tile16(dhs, R, H, False))
+        close(got, want, tol, "dhs")
+        par.assert_parity(got, want, dtype, par.row_blocks, "dhs")
+        assert np.all(got[ends] == 0) and np.all(np.abs(got[rows["half"]]).max(1) > 0)
 
 
 # ---- GEMM paths no other op test reaches (each against float64 on the rounded operands: tests/parity.py assert_product / assert_bits) ----

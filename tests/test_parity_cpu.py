@@ -253,3 +253,237 @@ def test_assert_parity_names_the_block_and_returns_the_ratios():
         par.assert_parity(bad, zero, BF16, par.row_blocks, "dlogits")
     with pytest.raises(AssertionError):
         par.assert_parity(np.full((2, 2), np.nan), np.ones((2, 2)), BF16, par.whole, "dh0")
+
+
+# ---- the saturated regime: clipped gates, tanh far out, clipped cross-entropy rows ------------------------------------------
+# The problems of parity.rnn_saturated_problem / softmax_head_clipped_problem at every shape the GPU tests run them at.  BOUNDS is
+# the table the smooth problems use: the same rounding model decides, and must stay below HALF of every bound here.
+SAT_CELLS = ["LSTM", "GRU", "SimpleRNN"]
+
+
+def f32r(a):
+    """float64 -> f32 -> float64"""
+    return np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
+
+
+def _sat(cellname, H, T, B, rnd=bf, xmode="dense"):
+    return par.rnn_saturated_problem(cellname, H, T, B, par.saturated_seed(H, T, B), rnd, xmode)
+
+
+def _sat_backward(cellname, pb, ext, seqs=None):
+    """(inputs of a BPTT run on the problem's rounded sequences - or on ``seqs`` - , the oracle's da, dh0, dc0)"""
+    hs, cs, acts = seqs if seqs is not None else (pb.hs_r, pb.cs_r, pb.acts_r)
+    args = (hs, cs, acts, pb.U, pb.dext if ext else None, pb.dlast)
+    da, _, dh0, dc0 = vo.rnn_backward(cellname, *args)
+    return args, (da, dh0, dc0)
+
+
+def check_backward_saturated(cellname, got, want, acts, dtype=BF16):
+    """what test_ops_gpu._rnn_backward_case checks on a saturated problem: the parity bounds and exact zeros at clipped gates"""
+    worst = check_backward(cellname, got, want, dtype)
+    par.assert_clipped_gates_have_no_gradient(cellname, acts, got[0], "da")
+    return worst
+
+
+def _sat_backward_cases(cellname):
+    """(H, T, B, ext) of every saturated BPTT case of test_ops_gpu.py / test_hidden_sizes_gpu.py"""
+    cases = [(H, par.SAT_T_BWD, B, ext) for H, B in par.SAT_BWD_SHAPES + par.SAT_WIDE_SHAPES for ext in (True, False)]
+    cases += [(256, T, 32, ext) for T in (3, 7) for ext in (True, False)]
+    if cellname in ("LSTM", "GRU"):
+        cases.append((par.SAT_LONG[0], par.SAT_LONG[1], par.SAT_LONG[2], True))
+    return cases
+
+
+def _worst(ratios):
+    return max(max(r["elem"], r["norm"]) if isinstance(r, dict) else r for r in ratios)
+
+
+@pytest.mark.parametrize("cellname", SAT_CELLS)
+def test_bf16_rounding_model_passes_the_bounds_on_saturated_problems(cellname):
+    """forward (dense and index input; the LSTM's long window with dense and constant input), BPTT on the oracle's rounded sequences,
+    and BPTT on the model's OWN forward sequences (the hand-over test).  Measured: profiles/r10_saturation_margins.txt."""
+    worst = {}
+    for H, B in par.SAT_FWD_SHAPES + par.SAT_WIDE_SHAPES:
+        for xmode in ("dense", "index"):
+            pb = _sat(cellname, H, par.SAT_T_FWD, B, xmode=xmode)
+            worst["forward H=%d B=%d %s" % (H, B, xmode)] = _worst(check_forward(
+                cellname, model_forward(cellname, pb.xp, pb.U, pb.h0, pb.c0), (pb.hs, pb.cs, pb.acts, pb.hs[-1])))
+    if cellname == "LSTM":
+        H, T, B = par.SAT_LONG
+        for xmode in ("dense", "const"):
+            pb = _sat(cellname, H, T, B, xmode=xmode)
+            worst["forward H=%d T=%d B=%d %s" % (H, T, B, xmode)] = _worst(check_forward(
+                cellname, model_forward(cellname, pb.xp, pb.U, pb.h0, pb.c0), (pb.hs, pb.cs, pb.acts, pb.hs[-1])))
+    for H, T, B, ext in _sat_backward_cases(cellname):
+        pb = _sat(cellname, H, T, B)
+        args, want = _sat_backward(cellname, pb, ext)
+        worst["BPTT H=%d T=%d B=%d ext=%d" % (H, T, B, ext)] = _worst(check_backward_saturated(
+            cellname, model_backward(cellname, *args), want, pb.acts_r))
+    if cellname != "SimpleRNN":
+        pb = _sat(cellname, 256, par.SAT_T_FWD, 32)
+        hs, cs, acts, _ = model_forward(cellname, pb.xp, pb.U, pb.h0, pb.c0)
+        args, want = _sat_backward(cellname, pb, True, (hs, cs, acts))
+        worst["hand-over H=256 T=9 B=32"] = _worst(check_backward_saturated(cellname, model_backward(cellname, *args), want, acts))
+    for k, v in worst.items():                           # (pytest -s shows them)
+        print("saturated model %-9s %-34s %.3f x the bound" % (cellname, k, v))
+    assert max(worst.values()) <= 0.5, max(worst.items(), key=lambda kv: kv[1])
+
+
+@pytest.mark.parametrize("cellname", ["LSTM", "GRU"])
+@pytest.mark.parametrize("rnd", [bf, f32r])
+def test_saturated_problems_are_saturated(cellname, rnd):
+    """at least 10 % of the hard-sigmoid gate values clipped at 0, and as many at 1, at every shape; the LSTM cell state of the long
+    window beyond 45 (e^{2c} leaves the f32 range at c = 44.4)"""
+    shapes = {(H, par.SAT_T_FWD, B) for H, B in par.SAT_FWD_SHAPES + par.SAT_WIDE_SHAPES} | {(H, T, B) for H, T, B, _ in _sat_backward_cases(cellname)}
+    for H, T, B in sorted(shapes):
+        for xmode in ("dense", "index"):
+            pb = _sat(cellname, H, T, B, rnd, xmode)
+            lo, hi = par.clipped_share(cellname, pb.acts_r)
+            print("clipped share %-4s %-5s H=%d T=%d B=%d %s: %.3f at 0, %.3f at 1" % (cellname, rnd.__name__, H, T, B, xmode, lo, hi))
+            assert lo >= 0.10 and hi >= 0.10, (H, T, B, xmode, lo, hi)
+    if cellname == "LSTM":
+        H, T, B = par.SAT_LONG
+        for xmode in ("dense", "const"):
+            pb = _sat(cellname, H, T, B, rnd, xmode)
+            assert np.abs(pb.cs).max() > 45 and np.all(np.isfinite(pb.hs)), (xmode, np.abs(pb.cs).max())
+
+
+@pytest.mark.parametrize("cellname", ["LSTM", "GRU"])
+def test_saturated_backward_defects_fail(cellname, monkeypatch):
+    """the derivative 0.2 at a clipped gate, at every BPTT shape: the parity bounds see it, and so does the exact-zero check"""
+    for H, T, B, ext in _sat_backward_cases(cellname):
+        pb = _sat(cellname, H, T, B)
+        args, want = _sat_backward(cellname, pb, ext)
+        check_backward_saturated(cellname, (bf(want[0]), want[1], want[2]), want, pb.acts_r)
+        with monkeypatch.context() as mp:
+            mp.setitem(vo._REC_ACT, "hard_sigmoid", (vo.hard_sigmoid, lambda y: 0.2 + 0.0 * y))
+            da, _, dh0, dc0 = vo.rnn_backward(cellname, *args)
+        _fails(check_backward, cellname, (da, dh0, dc0), want)
+        _fails(par.assert_clipped_gates_have_no_gradient, cellname, pb.acts_r, da)
+        _fails(par.assert_clipped_gates_have_no_gradient, cellname, pb.acts_r, da + 1e-30)
+
+
+@pytest.mark.parametrize("cellname", SAT_CELLS)
+def test_saturated_forward_defects_fail(cellname, monkeypatch):
+    """gates left unclipped; NaN where tanh of a planted row is +-1 (e^{2x} overflowing to inf / inf)"""
+    cases = [(H, par.SAT_T_FWD, B) for H, B in par.SAT_FWD_SHAPES + par.SAT_WIDE_SHAPES] + ([par.SAT_LONG] if cellname == "LSTM" else [])
+    for H, T, B in cases:
+        pb = _sat(cellname, H, T, B)
+        want = (pb.hs, pb.cs, pb.acts, pb.hs[-1])
+        check_forward(cellname, (bf(pb.hs), bf(pb.cs) if pb.cs is not None else None, bf(pb.acts), pb.hs[-1]), want)
+        if cellname != "SimpleRNN":
+            with monkeypatch.context() as mp:
+                mp.setitem(vo._REC_ACT, "hard_sigmoid", (lambda x: 0.2 * x + 0.5, vo._dhs))
+                hs, cs, acts = vo.rnn_forward(cellname, pb.xp, pb.U, pb.h0, pb.c0)
+            with np.errstate(over="ignore"):                  # (an unclipped LSTM cell state runs away)
+                _fails(check_forward, cellname, (hs, cs, acts, hs[-1]), want)
+        if B > 3:
+            tanh_gate = {"LSTM": np.s_[:, 1, 2 * H:3 * H], "GRU": np.s_[:, 1, 2 * H:], "SimpleRNN": np.s_[:, 1]}[cellname]
+            acts = pb.acts.copy()
+            assert np.all(acts[tanh_gate] == 1.0)
+            acts[tanh_gate] = np.nan
+            _fails(check_forward, cellname, (pb.hs, pb.cs, acts, pb.hs[-1]), want)
+            hs = pb.hs.copy()
+            hs[1:, 1] = np.nan                                   # ... or the state: tanh(c) of a cell state past 44.4
+            _fails(check_forward, cellname, (hs, pb.cs, pb.acts, hs[-1]), want)
+
+
+@pytest.mark.parametrize("key", sorted(par.CLIPPED_HEAD_SEEDS))
+@pytest.mark.parametrize("rnd", [bf, f32r])
+def test_clipped_softmax_head_problem_and_its_defects(key, rnd):
+    """the builder's probability bands hold at every case of the GPU tests (asserted inside the builder, on rounded operands); a
+    correct head passes test_softmax_head's checks and the planted defects fail them.  The HIGH clip changes a row's loss by
+    -log(1 - 1e-7) = 1e-7, which no loss check can see: that branch is covered by the gradient (exactly zero on such a row)."""
+    N, H, R, two_hot = key
+    rng, hs, W, bias, tgt, rw, tgt2, rows = par.softmax_head_clipped_problem(N, H, R, par.CLIPPED_HEAD_SEEDS[key], two_hot, rnd)
+    Wq = rnd(W)
+    low, high, inside = par.ce_bands(hs, Wq, bias, tgt, tgt2)
+    clipped = par.fully_clipped_rows(low, high, inside)
+    assert set(clipped) >= {rows["high"], rows["low"], rows["low_last_tile"]} and rows["low_last_tile"] >= 16 * ((R - 1) // 16)
+    assert low.any() and high.any() and inside.sum() > R // 2
+    if two_hot:
+        assert {"low_inside", "inside_low", "low_high", "high_low", "low_low"} <= set(rows)
+        assert set(clipped) >= {rows["low_high"], rows["high_low"], rows["low_low"]}
+    if R == 40:                    # the padding-rows variant (b_stride = 8, b_valid = 5) keeps the bands and the planted rows
+        t1, t2 = tgt.copy(), (tgt2.copy() if two_hot else None)
+        moved = par.retarget_padding_rows(hs, Wq, bias, t1, t2, np.arange(R) % 8 < 5, [5] + list(rows.values()))
+        bands = par.ce_bands(hs, Wq, bias, t1, t2)
+        assert len(moved) >= R // 4 and np.all(bands[2][moved, 0]) and set(par.fully_clipped_rows(*bands)) == set(clipped)
+    p, loss, dl, y = par.softmax_head_oracle(hs, Wq, bias, tgt, rw, 0.7, tgt2)
+    assert np.all(dl[clipped] == 0) and np.all(dl[5] == 0)
+    want = (p, dl, loss)
+    check_softmax_head((p.astype(np.float32), rnd(dl), np.float32(loss)), want, BF16 if rnd is bf else par.F32)
+    for dtype in (BF16, par.F32):
+        leak = 0.7 * rw[:, None] * (p * y.sum(1, keepdims=True) - y)                 # p - y on a clipped row
+        for row in clipped:
+            bad = dl.copy()
+            bad[row] = leak[row]
+            _fails(check_softmax_head, (p, bad, loss), want, dtype)
+        if two_hot:                                                                    # one target clipped: both dropped
+            for row in (rows["low_inside"], rows["inside_low"], rows["low_inside_last_tile"]):
+                assert np.abs(dl[row]).max() > 0
+                _fails(check_softmax_head, (p, _zero(dl, row), loss), want, dtype)
+        row = rows["low"]                                                             # loss from the unclipped log p
+        unclipped = loss + rw[row] * (-np.log(p[row, tgt[row]]) + np.log(vo.CE_EPS))
+        assert p[row, tgt[row]] < par.CE_FAR
+        _fails(check_softmax_head, (p, dl, unclipped), want, dtype)
+
+
+def model_head_f32(hs, Wq, bias, tgt, rw, grad_scale, tgt2, order):
+    """a correct head in float32: logits accumulated in float32 in one of par.product_models' orders, softmax, Keras' clipped
+    cross-entropy and its gradient evaluated in numpy float32.  Returns (probs, dlogits, loss)."""
+    f = np.float32
+    z = par.product_models(hs, Wq, bias=bias)[order].astype(f)
+    e = np.exp(z - z.max(1, keepdims=True), dtype=f)
+    p = e / e.sum(1, keepdims=True, dtype=f)
+    R, N = p.shape
+    dl, loss = np.zeros((R, N), f), f(0)
+    for t in (tgt, tgt2) if tgt2 is not None else (tgt,):
+        rows = np.nonzero(t < N)[0]
+        pt = p[rows, t[rows]]
+        inside = (pt >= f(vo.CE_EPS)) & (pt <= f(1) - f(vo.CE_EPS))
+        y = np.zeros((R, N), f)
+        y[rows[inside], t[rows[inside]]] = 1
+        g = np.zeros((R, N), f)
+        g[rows[inside]] = p[rows[inside]]
+        dl += f(grad_scale) * rw.astype(f)[:, None] * (g - y)
+        loss += np.sum(rw[rows].astype(f) * -np.log(np.clip(pt, f(vo.CE_EPS), f(1) - f(vo.CE_EPS)), dtype=f), dtype=f)
+    return p.astype(np.float64), dl.astype(np.float64), float(loss)
+
+
+@pytest.mark.parametrize("key", sorted(par.CLIPPED_HEAD_SEEDS))
+@pytest.mark.parametrize("rnd", [bf, f32r])
+def test_float32_model_of_a_correct_head_passes_the_bounds_on_clipped_rows(key, rnd):
+    """the f32 bound on forward values is 1e-5 normwise per row, and the relative error of a probability is the absolute error of
+    its logit: the planted rows must not ask more of an f32 kernel than f32 gives.  Worst of the accumulation orders: below half of
+    every f32 bound (f32-rounded operands; bf16-rounded ones, whose products are exact, as well)."""
+    N, H, R, two_hot = key
+    rng, hs, W, bias, tgt, rw, tgt2, rows = par.softmax_head_clipped_problem(N, H, R, par.CLIPPED_HEAD_SEEDS[key], two_hot, rnd)
+    Wq = rnd(W)
+    p, loss, dl, _ = par.softmax_head_oracle(hs, Wq, bias, tgt, rw, 0.7, tgt2)
+    for order in ("sequential", "tiles"):
+        got = model_head_f32(hs, Wq, bias, tgt, rw, 0.7, tgt2, order)
+        worst = _worst(check_softmax_head(got, (p, dl, loss), par.F32))
+        print("clipped head f32 model %s %s %s: %.3f x the bound" % (key, rnd.__name__, order, worst))
+        assert worst <= 0.5, (order, worst)
+
+
+@pytest.mark.parametrize("rnd", [bf, f32r])
+def test_saturated_sigmoid_head_problem(rnd):
+    """float64 on the planted rows: sigmoid(+100) is 1 to the last bit, sigmoid(-100) = 3.7e-44 (the f32 kernel returns exactly 0:
+    e^100 is inf), the zero-logit rows exactly 1/2 - rounded half-to-even to 0"""
+    hs, W, bias, y, rw, rows = par.sigmoid_head_saturated_problem(40, 64, 2, rnd)
+    p = vo.sigmoid(hs @ rnd(W) + bias)[:, 0]
+    assert np.all(p[rows["plus"]] == 1.0) and np.all(p[rows["minus"]] < 1e-40) and np.all(p[rows["half"]] == 0.5)
+    assert np.all(np.round(p[rows["half"]]) == 0.0) and list(y[rows["half"]]) == [0.0, 1.0]
+
+
+@pytest.mark.parametrize("cell", ["LSTM", "GRU"])
+def test_engine_saturated_problem_keeps_its_distance_from_the_clips(cell):
+    """test_engine_gpu's saturated problem: every pre-clip gate value of the float64 oracle at least 1e-4 from 0 and from 1, and at
+    least 5 % of the gate values of each of the 8 recurrences clipped"""
+    from tests import test_engine_gpu as eng_t
+    margins = eng_t._oracle_gate_margins(*eng_t._saturated_problem(cell))
+    assert len(margins) == 8
+    for share, dist in margins:
+        assert share >= eng_t.SATURATED_MIN_SHARE and dist >= eng_t.SATURATED_MIN_DISTANCE, margins
