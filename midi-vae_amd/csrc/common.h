@@ -144,6 +144,28 @@ __device__ __forceinline__ void lds_barrier() {
         if (e__ != hipSuccess) return MVAE_E_LAUNCH;          \
     } while (0)
 
+// Host: gfx950 has 160 KiB of LDS per CU, but dynamic LDS above 64 KiB must be requested per kernel
+// (hipFuncAttributeMaxDynamicSharedMemorySize) before the first such launch.  The kernel is a template parameter, so every kernel
+// has its own record of what it was granted: one request per kernel and process, another one only for a larger size.
+template <auto KERNEL>
+int mvae_grant_lds(size_t lds) {
+    static size_t granted = 64 * 1024;
+    if (lds > granted) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return MVAE_E_LAUNCH;
+        granted = lds;
+    }
+    return MVAE_OK;
+}
+// ... and the launch itself: MVAE_OK / MVAE_E_LAUNCH
+template <auto KERNEL, typename ARGS>
+int mvae_launch(dim3 grid, dim3 block, size_t lds, hipStream_t s, const ARGS& args) {
+    if (mvae_grant_lds<KERNEL>(lds) != MVAE_OK) return MVAE_E_LAUNCH;
+    hipLaunchKernelGGL(KERNEL, grid, block, lds, s, args);
+    MVAE_CHECK_LAUNCH();
+    return MVAE_OK;
+}
+
 // ---- device-side hand-over between RUNNING kernels (time-pipelined stacks, include/midivae_hip.h) -------------------
 // Single asm blocks with scalar control flow and one or two temporary VGPRs: as C++ (a thread-0 loop, barriers, an
 // atomic) they cost the 256-VGPR LSTM backward kernel registers it does not have, and an extra basic block in its step

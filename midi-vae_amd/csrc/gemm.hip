@@ -235,9 +235,7 @@ __global__ __launch_bounds__(256) void gemm_k(const mvae_gemm_args a) {
 #include "ablations.h"      // GEMM_ABL_* timing switches: all 0 in the product build
 // s_sleep argument of the persistent GEMMs' chunk polls (x 64 clocks between two system-scope loads of the counter): a chunk arrives
 // every ~40 us; 256 waves of such a launch polling every 0.2 us (8) is traffic on one memory channel that buys nothing
-#ifndef GEMM_POLL_SLEEP
-#define GEMM_POLL_SLEEP 32
-#endif
+constexpr int GEMM_POLL_SLEEP = 32;
 constexpr int FBM = 128, FBN = 128, FBK = 64;
 // k-contiguous image: [row][FBK + 8] (144-byte rows).  NOT conflict-free for ds_read_b128 - its four lane groups are non-contiguous
 // ({0-3, 12-15, 20-27}, ...: rows {0-3, 12-15} of one k chunk and rows {4-11} of the next share a group; PMC: SQ_LDS_BANK_CONFLICT 32-40 %
@@ -835,38 +833,21 @@ bool ws_ok(const mvae_gemm_args& a) {
 }
 int launch_ws(const mvae_gemm_args& a, hipStream_t s) {
     const size_t lds = (size_t)2 * WS_KT * f_img<false>() * sizeof(bf16_t);
-    static bool raised = false;
-    if (!raised) {
-        for (const void* f : {reinterpret_cast<const void*>(&proj_ws_k<0>), reinterpret_cast<const void*>(&proj_ws_k<1>),
-                              reinterpret_cast<const void*>(&proj_ws_k<2>)})
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return MVAE_E_LAUNCH;
-        raised = true;
-    }
     const dim3 grid((unsigned)a.max_blocks);
-    if (a.c_layout != MVAE_TILE16) hipLaunchKernelGGL(proj_ws_k<2>, grid, dim3(256), lds, s, a);
-    else if (a.chunk_done) hipLaunchKernelGGL(proj_ws_k<0>, grid, dim3(256), lds, s, a);
-    else hipLaunchKernelGGL(proj_ws_k<1>, grid, dim3(256), lds, s, a);
-    MVAE_CHECK_LAUNCH();
-    return MVAE_OK;
+    // (named in the order <0>, <1>, <2>: the order of first use is the order in which the three kernels are emitted)
+    if (a.c_layout == MVAE_TILE16 && a.chunk_done) return mvae_launch<proj_ws_k<0>>(grid, dim3(256), lds, s, a);
+    if (a.c_layout == MVAE_TILE16) return mvae_launch<proj_ws_k<1>>(grid, dim3(256), lds, s, a);
+    return mvae_launch<proj_ws_k<2>>(grid, dim3(256), lds, s, a);
 }
 
 template <bool A_RC, bool B_RC, bool ONEHOT, bool CS = false>
 int launch_fast(const mvae_gemm_args& a, hipStream_t s) {
     const size_t lds = (size_t)2 * (f_img<A_RC>() + f_img<B_RC>()) * sizeof(bf16_t);
-    static bool raised = false;
-    if (!raised && lds > 64 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_fast_k<A_RC, B_RC, ONEHOT, CS>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return MVAE_E_LAUNCH;
-        raised = true;
-    }
     const int sk = a.split_k > 1 ? a.split_k : 1;
     long long tiles = (long long)((a.N + FBN - 1) / FBN) * ((a.M + FBM - 1) / FBM) * (sk >= 8 ? (sk + 7) / 8 * 8 : sk);
     if (a.max_blocks > 0 && tiles > a.max_blocks) tiles = a.max_blocks;
     if (a.chunk_rows) tiles = a.max_blocks;          // persistent grid: every workgroup passes through every chunk
-    hipLaunchKernelGGL((gemm_fast_k<A_RC, B_RC, ONEHOT, CS>), dim3((unsigned)tiles), dim3(256), lds, s, a);
-    MVAE_CHECK_LAUNCH();
-    return MVAE_OK;
+    return mvae_launch<gemm_fast_k<A_RC, B_RC, ONEHOT, CS>>(dim3((unsigned)tiles), dim3(256), lds, s, a);
 }
 
 // true when the fast kernel can take this problem
@@ -967,16 +948,7 @@ extern "C" int mvae_gemm_kstream_multi(const mvae_gemm_args* problems, int32_t n
     m.base[n] = (int32_t)total;
     if (total > 256) return MVAE_E_ARG;         // all of them wait for the producers: they must fit beside them
     const size_t lds = (size_t)2 * (f_img<true>() + f_img<true>()) * sizeof(bf16_t);
-    static bool raised = false;
-    if (!raised && lds > 64 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kstream_multi_k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess)
-            return MVAE_E_LAUNCH;
-        raised = true;
-    }
-    hipLaunchKernelGGL(gemm_kstream_multi_k, dim3((unsigned)total), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), m);
-    MVAE_CHECK_LAUNCH();
-    return MVAE_OK;
+    return mvae_launch<gemm_kstream_multi_k>(dim3((unsigned)total), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), m);
 }
 
 extern "C" int mvae_gemm_multi(const mvae_gemm_args* problems, int32_t n, void* stream) {
@@ -1008,16 +980,7 @@ extern "C" int mvae_gemm_multi(const mvae_gemm_args* problems, int32_t n, void* 
     }
     m.base[n] = (int32_t)total;
     const size_t lds = (size_t)2 * (f_img<true>() + f_img<true>()) * sizeof(bf16_t);
-    static bool raised = false;
-    if (!raised && lds > 64 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_multi_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-            hipSuccess)
-            return MVAE_E_LAUNCH;
-        raised = true;
-    }
-    hipLaunchKernelGGL(gemm_multi_k, dim3((unsigned)total), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), m);
-    MVAE_CHECK_LAUNCH();
-    return MVAE_OK;
+    return mvae_launch<gemm_multi_k>(dim3((unsigned)total), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), m);
 }
 
 extern "C" int mvae_occupancy(int32_t which) {
@@ -1026,17 +989,17 @@ extern "C" int mvae_occupancy(int32_t which) {
     if (which == 0) {            // the dX GEMM between two pipelined layers: da (R, G*H) x W (H, G*H)^T, both k-contiguous
         const size_t lds = (size_t)2 * (f_img<false>() + f_img<false>()) * sizeof(bf16_t);
         const void* f = reinterpret_cast<const void*>(&gemm_fast_k<false, false, false, false>);
-        if (lds > 64 * 1024 && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return MVAE_E_LAUNCH;
+        if (mvae_grant_lds<gemm_fast_k<false, false, false, false>>(lds) != MVAE_OK) return MVAE_E_LAUNCH;
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, 256, lds);
     } else if (which == 1) {
         const size_t lds = (size_t)2 * WS_KT * f_img<false>() * sizeof(bf16_t);
         const void* f = reinterpret_cast<const void*>(&proj_ws_k<0>);
-        if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return MVAE_E_LAUNCH;
+        if (mvae_grant_lds<proj_ws_k<0>>(lds) != MVAE_OK) return MVAE_E_LAUNCH;
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, 256, lds);
     } else if (which == 2) {
         const size_t lds = (size_t)2 * (f_img<true>() + f_img<true>()) * sizeof(bf16_t);
         const void* f = reinterpret_cast<const void*>(&gemm_kstream_multi_k);
-        if (lds > 64 * 1024 && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return MVAE_E_LAUNCH;
+        if (mvae_grant_lds<gemm_kstream_multi_k>(lds) != MVAE_OK) return MVAE_E_LAUNCH;
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, 256, lds);
     } else return MVAE_E_ARG;
     return e == hipSuccess ? n : MVAE_E_LAUNCH;

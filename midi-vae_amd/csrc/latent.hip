@@ -274,16 +274,8 @@ extern "C" int mvae_latent_chain_fwd(const mvae_latent_chain_fwd_args* a, void* 
     if (a->w_init && (a->n_init % 4)) return MVAE_E_ARG;
     const size_t lds = fwd_lds(*a);
     if (lds > 160 * 1024) return MVAE_E_UNSUPPORTED;
-    static bool raised = false;
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&latent_chain_fwd_k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess)
-            return MVAE_E_LAUNCH;
-        raised = true;
-    }
-    hipLaunchKernelGGL(latent_chain_fwd_k, dim3(a->B / LR), dim3(LT), lds, reinterpret_cast<hipStream_t>(stream), *a);
-    MVAE_CHECK_LAUNCH();
-    return MVAE_OK;
+    // (lds varies with the problem: the launch helper requests more than 64 KiB once per size that exceeds the last one granted)
+    return mvae_launch<latent_chain_fwd_k>(dim3(a->B / LR), dim3(LT), lds, reinterpret_cast<hipStream_t>(stream), *a);
 }
 
 extern "C" int mvae_latent_chain_bwd(const mvae_latent_chain_bwd_args* a, void* stream) {
@@ -295,14 +287,6 @@ extern "C" int mvae_latent_chain_bwd(const mvae_latent_chain_bwd_args* a, void* 
     if (!a->wt_pack && a->ncat != 1) return MVAE_E_ARG;
     const size_t lds = bwd_lds(*a);
     if (lds > 160 * 1024) return MVAE_E_UNSUPPORTED;
-    static bool raised = false;
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&latent_chain_bwd_k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess)
-            return MVAE_E_LAUNCH;
-        raised = true;
-    }
-    hipLaunchKernelGGL(latent_chain_bwd_k, dim3(a->B / LR), dim3(LT), lds, reinterpret_cast<hipStream_t>(stream), *a);
-    MVAE_CHECK_LAUNCH();
-    return MVAE_OK;
+    // (lds varies with the problem, as in mvae_latent_chain_fwd)
+    return mvae_launch<latent_chain_bwd_k>(dim3(a->B / LR), dim3(LT), lds, reinterpret_cast<hipStream_t>(stream), *a);
 }

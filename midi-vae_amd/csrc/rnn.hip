@@ -500,18 +500,7 @@ int launch_fwd(const mvae_rnn_fwd_args& a, hipStream_t s) {
     constexpr int LDH = H + lds_pad<WT>::value;
     size_t lds = (size_t)(2 + (CELL == MVAE_GRU ? 1 : 0)) * 16 * LDH * sizeof(WT);
     if (XMODE == MVAE_X_SCALAR) lds += (size_t)2 * G * H * sizeof(float);
-    if (lds > 64 * 1024) {
-        static bool raised = false;   // gfx950 has 160 KiB of LDS per CU; anything above 64 KiB must be requested
-        if (!raised) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&rnn_fwd_k<CELL, WT, XMODE, NT, NW>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return MVAE_E_LAUNCH;
-            raised = true;
-        }
-    }
-    hipLaunchKernelGGL((rnn_fwd_k<CELL, WT, XMODE, NT, NW>), dim3((a.B + 15) / 16), dim3(NW * 64), lds, s, a);
-    MVAE_CHECK_LAUNCH();
-    return MVAE_OK;
+    return mvae_launch<rnn_fwd_k<CELL, WT, XMODE, NT, NW>>(dim3((a.B + 15) / 16), dim3(NW * 64), lds, s, a);
 }
 // unit tiles per wave x waves: the 4 SIMDs get equal shares of the H / 16 tiles; two waves per SIMD where they fit
 template <int CELL, typename WT, int XMODE>
@@ -554,18 +543,7 @@ template <int CELL, typename WT, int NT, int NW = 4>
 int launch_bwd(const mvae_rnn_bwd_args& a, hipStream_t s) {
     constexpr int GH = mvae_gates(CELL) * NT * 16 * NW;
     const size_t lds = (size_t)16 * (GH + lds_pad<WT>::value) * sizeof(WT);
-    if (lds > 64 * 1024) {
-        static bool raised = false;
-        if (!raised) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&rnn_bwd_k<CELL, WT, NT, NW>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return MVAE_E_LAUNCH;
-            raised = true;
-        }
-    }
-    hipLaunchKernelGGL((rnn_bwd_k<CELL, WT, NT, NW>), dim3((a.B + 15) / 16), dim3(NW * 64), lds, s, a);
-    MVAE_CHECK_LAUNCH();
-    return MVAE_OK;
+    return mvae_launch<rnn_bwd_k<CELL, WT, NT, NW>>(dim3((a.B + 15) / 16), dim3(NW * 64), lds, s, a);
 }
 template <int CELL, typename WT>
 int bwd_nt(const mvae_rnn_bwd_args& a, hipStream_t s) {

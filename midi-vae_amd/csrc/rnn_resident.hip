@@ -28,10 +28,11 @@
 //    Row-major OUTPUTS consumed by the GEMMs (h sequence, da, r*h) are first assembled in LDS - where the step
 //    needs them anyway - and written back as whole 512-byte row segments.
 //
-//  * Forward LSTM schedule: the gate arithmetic of unit tile n-1 is issued among the MFMA groups of tile n (the
-//    matrix pipe runs a 4-MFMA group for 64 cycles), so only the last tile's arithmetic and the barrier are
-//    exposed.  Backward has a true dependency (all of dh before any gate gradient) and stays phased.
-#include "common.h"
+//  * Forward LSTM schedule (the slot-interleaved kernels): the gate arithmetic of unit tile n-1 is issued among the
+//    MFMAs of tile n, so only the last tile's arithmetic and the barrier are exposed; the phased kernel rnn_fwd_res_k
+//    keeps one accumulator set and runs a tile's arithmetic behind its own MFMAs.  Backward has a true dependency
+//    (all of dh before any gate gradient) and stays phased.
+#include "rnn_res_common.h"
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -52,15 +53,13 @@ extern "C" int mvae_debug_stamps(unsigned long long* out) {
 #define STAMP(k)
 #endif
 
-#include "ablations.h"      // ABL_* timing switches: all 0 in the product build (variant builds only: tools/build_variants.sh)
+#include "ablations.h"      // ABL_* / GB_* timing switches: all 0 in the product build (variant builds only: tools/build_variants.sh)
 
 namespace {
 
 constexpr int RH = 256;           // hidden size this file is specialised for
 constexpr int RS = RH / 32;       // k-groups of the forward contraction (8)
 constexpr int RNT = 4;            // unit tiles (16 units) per wave
-
-typedef u16x8 frag;
 
 // ---- inline-asm building blocks ---------------------------------------------------------------------------
 // Four MFMAs sharing one B fragment.  hipcc neither pads hazards inside an asm statement nor models the MFMA:
@@ -110,44 +109,15 @@ __device__ __forceinline__ void load4_agpr_nowait(frag& u0, frag& u1, frag& u2, 
 __device__ __forceinline__ void aload8(u16x4& d, const void* p) { d = *reinterpret_cast<const u16x4*>(p); }
 __device__ __forceinline__ void aload4(float& d, const void* p) { d = *reinterpret_cast<const float*>(p); }
 __device__ __forceinline__ void aload1(int& d, const void* p) { d = *reinterpret_cast<const uint8_t*>(p); }
-__device__ __forceinline__ void vm_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 // ties asm-loaded registers to the drain: consumers can only be scheduled after this statement
 __device__ __forceinline__ void pin4(u16x4& a, u16x4& b, u16x4& c, u16x4& d) {
     asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
 }
-// LSTM BPTT filler slots (tools/build_variants.sh for A/B; profiles/r03_r_bptt_slots.txt): the write-through da stores as LATE as
-// the staging registers allow - slots 16.. cost +0.33 ms per train step, 44 +0.03, 50 (round 2) 0, 58 -0.05: stores in flight slow
-// the return of the next step's prefetched values more than their acknowledgement is missed at the T-fragment drain
-#ifndef BWL_LOAD_STRIDE
-#define BWL_LOAD_STRIDE 3
-#endif
-#ifndef BWL_COPY_SLOT
-#define BWL_COPY_SLOT 58
-#endif
-#ifndef BWL_OLD_DHS
-#define BWL_OLD_DHS 0
-#endif
-#ifndef BWL_COPY_STRIDE
-#define BWL_COPY_STRIDE 4
-#endif
-#ifndef GB_DRAIN
-#define GB_DRAIN 0
-#endif
-// a wave-uniform pointer the compiler has lost track of (state captured by a step lambda), back in scalar registers
-template <typename T>
-__device__ __forceinline__ T* uniform_ptr(T* p) {
-    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return reinterpret_cast<T*>(((unsigned long long)hi << 32) | lo);
-}
-#ifndef GRU_NVB
-#define GRU_NVB 24     // candidate fragments of the GRU forward kernel held in vector registers (of 32; the rest in LDS)
-#endif
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <int E>
 __device__ __forceinline__ f32x2 lo_hi(const f32x4& v) { return __builtin_shufflevector(v, v, E, E + 1); }
-// 4-element forms of tanh_fast / dhard_sigmoid (common.h): the same operations per element, written on vectors so that
-// the multiplies / adds / fmas become packed instructions
+// 4-element form of tanh_fast (common.h): the same operations per element, written on vectors so that the multiplies /
+// adds / fmas become packed instructions
 __device__ __forceinline__ f32x4 tanh_fast4(f32x4 x) {
     const f32x4 t = x * 2.8853900817779268f;
     const f32x4 e = {__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1]), __builtin_amdgcn_exp2f(t[2]), __builtin_amdgcn_exp2f(t[3])};
@@ -155,47 +125,10 @@ __device__ __forceinline__ f32x4 tanh_fast4(f32x4 x) {
     const f32x4 rc = {__builtin_amdgcn_rcpf(s1[0]), __builtin_amdgcn_rcpf(s1[1]), __builtin_amdgcn_rcpf(s1[2]), __builtin_amdgcn_rcpf(s1[3])};
     return 1.0f - 2.0f * rc;
 }
-__device__ __forceinline__ f32x4 dhard_sigmoid4(f32x4 y) {
-    const f32x4 sq = (y - y * y) * 0x1p100f;
-    return f32x4{__builtin_amdgcn_fmed3f(sq[0], 0.0f, 0.2f), __builtin_amdgcn_fmed3f(sq[1], 0.0f, 0.2f),
-                 __builtin_amdgcn_fmed3f(sq[2], 0.0f, 0.2f), __builtin_amdgcn_fmed3f(sq[3], 0.0f, 0.2f)};
-}
 // The derivative of hard_sigmoid at a saved gate value y in [0, 1] is 0.2 where 0 < y < 1.  sat4(y) = 0.2 * 2^-100 there, else 0:
 // y - y^2 is 0 exactly at the two clipped values and >= 2^-26 anywhere else a bf16 hard_sigmoid output can be, so one clamp
 // against a tiny constant selects (round 4: the factor 2^100 that makes it 0.2 rides on the OTHER factor of the product - one
 // multiply per element for all gates - and the negation is an operand modifier instead of the two v_xor hipcc emits).
-// bf16 -> f32 on the MATRIX pipe (round 4).  In the gate-gradient phase of the backward kernels no MFMA is in flight and the one
-// wave per SIMD is VALU-bound; a quarter of its instructions only widen saved bf16 values (v_lshlrev / v_and per element).
-// v_mfma_f32_16x16x16_bf16 with the 16x16 IDENTITY as A returns its B operand widened: lane (q, r) holds B[k = 4q + i][n = r] and
-// receives C[m = 4q + i][n = r] = sum_k I[m][k] B[k][r] = its own four elements, exactly (1.0 * x, fifteen zero products), plus the
-// accumulator operand - one issue slot for four elements and an addition.  (A non-finite value anywhere in the 16 lanes of a
-// column would spread as 0 * inf = NaN; saved activations are finite, or the step is lost already.)
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ s16x4 identity_fragment(int l) {
-    const int q = l >> 4, r = l & 15, j = r - 4 * q;
-    return s16x4{(short)(j == 0 ? 0x3F80 : 0), (short)(j == 1 ? 0x3F80 : 0), (short)(j == 2 ? 0x3F80 : 0), (short)(j == 3 ? 0x3F80 : 0)};
-}
-__device__ __forceinline__ f32x4 widen4(s16x4 ident, u16x4 packed, f32x4 plus) {
-    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ident, __builtin_bit_cast(s16x4, packed), plus, 0, 0, 0);
-}
-#ifndef FWL_MFMA_WIDEN
-#define FWL_MFMA_WIDEN 0     /* LSTM forward, single-launch inference variants: tiles 1..3 start their accumulators at x through widen4 (48 VALU per step less) - measured SLOWER (const input, no saves: 2.01 vs 1.94 us per step: 12 more MFMAs on a pipe the step is already waiting for); the training variants (252 VGPRs) and the phase launches spill with it */
-#endif
-#ifndef BWL_ASM_1MSQ
-#define BWL_ASM_1MSQ 1
-#endif
-#ifndef BWL_MFMA_FIRST
-#define BWL_MFMA_FIRST 0      /* C = 0 inline in the first MFMA of each chain instead of zeroed accumulators: 8 v_mov_b64 less, but 2.78 vs 2.71 us per step (profiles/r04_h_bptt_ab.txt) */
-#endif
-#ifndef RES_WGMAJOR
-#define RES_WGMAJOR 0
-#endif
-#ifndef BWL_E_TILE_FENCE
-#define BWL_E_TILE_FENCE 0
-#endif
-#ifndef BWL_MFMA_WIDEN
-#define BWL_MFMA_WIDEN 0      /* 1: the upstream gradient only, 2: every saved value - both spill in the LSTM kernel (254 VGPRs + 256 AGPRs without them): profiles/r04_d_bptt_e_phase.txt */
-#endif
 #define DHS_TINY 0x1.99999ap-103f      /* 0.2f * 2^-100 */
 #define DHS_BIG 0x1p100f
 __device__ __forceinline__ f32x2 y_minus_y2(f32x2 y) {
@@ -218,16 +151,7 @@ __device__ __forceinline__ f32x4 sat4(f32x4 y) {
     return f32x4{__builtin_amdgcn_fmed3f(a[0], 0.0f, DHS_TINY), __builtin_amdgcn_fmed3f(a[1], 0.0f, DHS_TINY),
                  __builtin_amdgcn_fmed3f(b[0], 0.0f, DHS_TINY), __builtin_amdgcn_fmed3f(b[1], 0.0f, DHS_TINY)};
 }
-__device__ __forceinline__ u16x8 cat8(u16x4 a, u16x4 b) { return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7); }
-__device__ __forceinline__ void pin1(u16x4& a) { asm volatile("" : "+v"(a)); }
 __device__ __forceinline__ void pinf(float& a) { asm volatile("" : "+v"(a)); }
-__device__ __forceinline__ void pini(int& a) { asm volatile("" : "+v"(a)); }
-
-__device__ __forceinline__ f32x4 unpack4(u16x4 p) { return f32x4{bf2f(p[0]), bf2f(p[1]), bf2f(p[2]), bf2f(p[3])}; }
-__device__ __forceinline__ u16x4 pack4(f32x4 v) {
-    typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-    return __builtin_bit_cast(u16x4, __builtin_convertvector(v, bf16x4));     // 2 x v_cvt_pk_bf16_f32
-}
 
 // ---- fragment residency -----------------------------------------------------------------------------------
 #define RES_DECLARE_U(FPW_)                                                                                        \
@@ -284,23 +208,7 @@ __device__ __forceinline__ u16x4 pack4(f32x4 v) {
     } while (0)
 #define RES_NOHOOK(gi)
 
-enum { SAVE_NONE = 0, SAVE_HS = 1, SAVE_ALL = 2 };
 __device__ __forceinline__ int t_next2(int t, int T) { return t + 2 < T ? t + 2 : T - 1; }
-// Wave skew (round 4): the four waves of a workgroup leave every barrier together and run the same instruction stream, so their
-// memory instructions reach the CU's one address unit (and their LDS accesses the LDS) in the same cycles and queue behind each
-// other.  Wave w idles RES_WSKEW x 16 x w cycles behind the barrier that opens a memory-heavy phase: the streams stay de-phased
-// until the next barrier (A/B: profiles/r04_b_wave_skew.txt).
-#ifndef RES_WSKEW
-#define RES_WSKEW 0
-#endif
-__device__ __forceinline__ void res_skew(int w) {
-#if RES_WSKEW > 0
-    for (int i = 0; i < w; ++i) {
-#pragma unroll
-        for (int j = 0; j < RES_WSKEW; ++j) asm volatile("s_nop 15" ::: "memory");
-    }
-#endif
-}
 __device__ __forceinline__ void res_barrier() {
     if (ABL_NOBAR) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     else lds_barrier();
@@ -423,6 +331,7 @@ __global__ __launch_bounds__(256, 1) void rnn_fwd_res_k(const mvae_rnn_fwd_args 
         auto hfrag = [&](const bf16_t* tile, int ks) -> frag {
             return *reinterpret_cast<const frag*>(tile + sw_off<RH>(r, ks * 32 + q * 8));
         };
+#define HF_(ks) hfrag(htile, ks)
         // saved-sequence slot t (= h_{t-1}; slot 0 = h0): whole rows straight from the LDS tile
         if (SAVE >= SAVE_HS) tile_rows_to_global<RH>(htile, hs + ((size_t)t * B + blockIdx.x * 16) * RH, w, l);
         const size_t otile = ((size_t)t * tiles_per_step + blockIdx.x);          // TILE16 row tile of step t
@@ -494,46 +403,17 @@ __global__ __launch_bounds__(256, 1) void rnn_fwd_res_k(const mvae_rnn_fwd_args 
                     if (a.c_last) *reinterpret_cast<f32x4*>(a.c_last + (size_t)b * ldl + ub[n]) = creg[n];
                 }
             };
-#if RES_LSTM_PIPELINE
-            // software pipeline over unit tiles: MFMAs of tile n with the arithmetic of tile n-1 issued among them
-            f32x4 accA[4], accB[4];
-#pragma unroll
-            for (int n = 0; n <= RNT; ++n) {
-                f32x4* acc = (n & 1) ? accB : accA;
-                f32x4* prev = (n & 1) ? accA : accB;
-                if (n < RNT) {
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-#define HF_(ks) hfrag(htile, ks)
-#define LSTM_HOOK_(gi)                                                         \
-    if ((gi) == 1 && n > 0) {                                                 \
-        if (n == 1) step_inputs_ready();                                      \
-        lstm_tile(n - 1, prev[0], prev[1], prev[2], prev[3]);                 \
-        request_next(n - 1);                                                  \
-    }
-                    RES_PHASE(acc[0], acc[1], acc[2], acc[3], n * RS * 4, RS, HF_, LSTM_HOOK_);
-                    STAMP(8 + n);
-                } else {
-                    lstm_tile(n - 1, prev[0], prev[1], prev[2], prev[3]);
-                    request_next(n - 1);
-                }
-            }
-#else
             // register-lean schedule: one accumulator set; the gate arithmetic of a tile follows its own MFMAs
 #pragma unroll
             for (int n = 0; n < RNT; ++n) {
                 f32x4 acc[4];
 #pragma unroll
                 for (int g = 0; g < 4; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-#ifndef HF_
-#define HF_(ks) hfrag(htile, ks)
-#endif
                 RES_PHASE(acc[0], acc[1], acc[2], acc[3], n * RS * 4, RS, HF_, RES_NOHOOK);
                 if (n == 0) step_inputs_ready();
                 lstm_tile(n, acc[0], acc[1], acc[2], acc[3]);
                 request_next(n);
             }
-#endif
         } else {
             // ---- GRU phase A: z, r for tile pairs -------------------------------------------------------------
             f32x4 zg[RNT], rg[RNT];
@@ -544,9 +424,6 @@ __global__ __launch_bounds__(256, 1) void rnn_fwd_res_k(const mvae_rnn_fwd_args 
                 for (int nn = 0; nn < 2; ++nn)
 #pragma unroll
                     for (int g = 0; g < 2; ++g) acc[nn][g] = f32x4{0.f, 0.f, 0.f, 0.f};
-#ifndef HF_
-#define HF_(ks) hfrag(htile, ks)
-#endif
                 RES_PHASE(acc[0][0], acc[0][1], acc[1][0], acc[1][1], np * RS * 4, RS, HF_, RES_NOHOOK);
                 if (np == 0) step_inputs_ready();
 #pragma unroll
@@ -614,38 +491,9 @@ __global__ __launch_bounds__(256, 1) void rnn_fwd_res_k(const mvae_rnn_fwd_args 
 // statements ("pins") on the piece's operands keep hipcc from moving a piece out of its slot: volatile statements
 // keep their order, and a piece sits between the pin that defines its inputs and the pin that uses its outputs.
 // Global addresses are a wave-uniform base (SGPR pair) + one per-lane 32-bit offset + immediates.
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-#define SF_LAMBDA(ic) [&](auto ic) __attribute__((always_inline))
-template <bool AG>
-__device__ __forceinline__ void mfma1(f32x4& c, const frag& u, const frag& b) {
-    if (AG) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c) : "a"(u), "v"(b));
-    else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(u), "v"(b));
-}
-// the first MFMA of an accumulation chain: C = 0 as the instruction's inline constant instead of a zeroed register quad
-// (round 4: 8 v_mov_b64 per step and four registers of zeros less in the LSTM BPTT kernel)
-__device__ __forceinline__ void mfma1_first(f32x4& c, const frag& u, const frag& b) {
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&v"(c) : "v"(u), "v"(b));
-}
+// (static_for / SF_LAMBDA, mfma1, the pins and the global-pointer helpers: rnn_res_common.h)
 __device__ __forceinline__ void pinv(f32x4& v) { asm volatile("" : "+v"(v)); }
 __device__ __forceinline__ void pinq(frag& v) { asm volatile("" : "+v"(v)); }
-__device__ __forceinline__ void pinu(unsigned& v) { asm volatile("" : "+v"(v)); }
-// explicitly global (address space 1) views: a pointer that went through an asm pin is no longer provably global,
-// and hipcc would fall back to flat_ instructions
-typedef __attribute__((address_space(1))) unsigned char gbyte;
-typedef __attribute__((address_space(1))) u16x4 g_u16x4;
-typedef __attribute__((address_space(1))) u16x8 g_u16x8;
-__device__ __forceinline__ gbyte* to_global(const void* p) { return (gbyte*)(const_cast<void*>(p)); }
-__device__ __forceinline__ void pins(gbyte*& p) { asm volatile("" : "+s"(p)); }
-// the data a pipelined stack hands over (saved h rows forward, gate gradients backward) leaves WRITE-THROUGH (common.h)
-__device__ __forceinline__ void store16_wt(gbyte* uniform_base, unsigned lane_off, u16x8 v) {
-    ::store16_wt((const void*)uniform_base, lane_off, v);
-}
 
 // Residency class of the 32 fragment groups of a step (group = the 4 gate fragments of one k-group of one unit tile, in
 // order of use).  CLS_T: group 7 (tile 0's last).  With the NLG groups that live in LDS all at the end of the step (F0 = 32 -
@@ -669,11 +517,9 @@ struct lstm_group_map {
         }
     }
 };
-#ifndef LSTM_L_FIRST
-#define LSTM_L_FIRST 12
-#endif
+constexpr int LSTM_L_FIRST = 12;
 
-template <int XMODE, int SAVE, int NA, int NV, bool WIDEN = false>
+template <int XMODE, int SAVE, int NA, int NV>
 __device__ __forceinline__ void lstm_fwd_il_body(const mvae_rnn_fwd_args& a, const unsigned bx) {
     constexpr int G = 4, GH = G * RH;
     constexpr int FPW = G * RNT * RS, NGRP = FPW / 4;
@@ -739,7 +585,7 @@ __device__ __forceinline__ void lstm_fwd_il_body(const mvae_rnn_fwd_args& a, con
         *reinterpret_cast<u16x4*>(hbuf + (hw0 ^ (n << 5))) = pack4(h0v);
         if (SAVE == SAVE_ALL)      // c_0 -> slot 0 of the (T+1, B, H) TILE16P array: 8 bytes of the lane's 16 per tile pair
             *reinterpret_cast<u16x4*>(reinterpret_cast<unsigned char*>(a.cs) +
-                                      ((size_t)bx * (RES_WGMAJOR ? (T + 1) : 1) * (RH / 32) + w * 2 + (n >> 1)) * 1024 + (unsigned)l * 16u + (n & 1) * 8) = pack4(creg[n]);
+                                      ((size_t)bx * (RH / 32) + w * 2 + (n >> 1)) * 1024 + (unsigned)l * 16u + (n & 1) * 8) = pack4(creg[n]);
     }
 
     // ---- x queue (packed bf16x4 per tile and gate) for the step about to be computed --------------------------
@@ -786,7 +632,6 @@ __device__ __forceinline__ void lstm_fwd_il_body(const mvae_rnn_fwd_args& a, con
     constexpr float K2 = 2.8853900817779268f;   // 2 / ln 2
     f32x4 accA[4], accB[4], hn = {0.f, 0.f, 0.f, 0.f};
     frag bq[3], lt[4];
-    const s16x4 ident = identity_fragment(l);   // (FWL_MFMA_WIDEN: x -> f32 accumulators on the matrix pipe)
     auto request_t = [&]() __attribute__((always_inline)) {      // T fragments into the idle accumulator set
 #pragma unroll
         for (int g = 0; g < 4; ++g) accB[g] = __builtin_bit_cast(f32x4, tsrc[(size_t)g * (RH / 16) * RS * 64]);
@@ -798,13 +643,8 @@ __device__ __forceinline__ void lstm_fwd_il_body(const mvae_rnn_fwd_args& a, con
     gbyte *acts_p[G], *cs_p, *hs_p;              // step t:   saved gates (per gate), c_t (slot t+1), h_{t-1} (slot t)
     gbyte* x_p[G];                               // step t+1: inputs (per gate)
     const size_t x_step = tps * (GH / 16) * 512, hs_step = (size_t)B * RH * 2;
-#if RES_WGMAJOR     // (experiment: saved activations workgroup-major - a workgroup's steps contiguous - instead of time-major)
-    const size_t acts_step = (size_t)(GH / 32) * 1024, cs_step = (size_t)(RH / 32) * 1024;
-    const size_t acts_b0 = (size_t)bx * T * (GH / 32), cs_b0 = (size_t)bx * (T + 1) * (RH / 32);
-#else
     const size_t acts_step = x_step, cs_step = tps * (RH / 16) * 512;
     const size_t acts_b0 = (size_t)bx * (GH / 32), cs_b0 = (size_t)bx * (RH / 32);
-#endif
 #pragma unroll
     for (int g = 0; g < G; ++g) {
         acts_p[g] = to_global(a.acts) + (acts_b0 + g * (RH / 32) + w * 2) * 1024;
@@ -944,7 +784,7 @@ __device__ __forceinline__ void lstm_fwd_il_body(const mvae_rnn_fwd_args& a, con
                 if constexpr (n == 1) asm volatile("s_nop 3");     // the T fragments were MFMA operands a moment ago
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
-                    acc[g] = WIDEN ? widen4(ident, xq[n][g], f32x4{0.f, 0.f, 0.f, 0.f}) : unpack4(xq[n][g]);
+                    acc[g] = unpack4(xq[n][g]);
             }
             static_for<0, 32>(SF_LAMBDA(slc) {
                 constexpr int sl = decltype(slc)::value;
@@ -1006,7 +846,6 @@ __device__ __forceinline__ void lstm_fwd_il_body(const mvae_rnn_fwd_args& a, con
         tl0 ^= 8192u;
         STAMP(6);
         res_barrier();
-        res_skew(w);
         STAMP(7);
         // pipelined stack: hs slot t (= h_{t-1}) left this step, so the chunk ending at step t-1 is complete
         if (cs_steps && t == phi) {
@@ -1024,9 +863,7 @@ __device__ __forceinline__ void lstm_fwd_il_body(const mvae_rnn_fwd_args& a, con
 }
 template <int XMODE, int SAVE, int NA, int NV>
 __global__ __launch_bounds__(256, 1) void lstm_fwd_il_k(const mvae_rnn_fwd_args a) {
-    // (x -> accumulators through widen4 in the single-launch inference variants: the training variants sit at 252 VGPRs and the phase
-    //  launches' bodies share their registers with the dispatch - both spill with it)
-    lstm_fwd_il_body<XMODE, SAVE, NA, NV, FWL_MFMA_WIDEN && SAVE != SAVE_ALL>(a, blockIdx.x);
+    lstm_fwd_il_body<XMODE, SAVE, NA, NV>(a, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1043,6 +880,7 @@ __global__ __launch_bounds__(256, 1) void lstm_fwd_il_k(const mvae_rnn_fwd_args 
 //             the gaps of the second half carry tanh + the h update of tiles 0,1
 //          -  tanh + h update of tiles 2,3, barrier
 // Inputs are TILE16, saved activations (z, r, candidate) TILE16P: one 16-byte store per gate and tile pair.
+constexpr int GRU_NVB = 24;     // candidate fragments held in vector registers (of 32; the rest in LDS)
 template <int XMODE, int SAVE>
 __device__ __forceinline__ void gru_fwd_il_body(const mvae_rnn_fwd_args& a, const unsigned bx) {
     constexpr int G = 3, GH = G * RH, NLc = RNT * RS;             // 32 candidate fragments per wave in LDS
@@ -1554,9 +1392,6 @@ __global__ __launch_bounds__(256, 1) void rnn_bwd_res_k(const mvae_rnn_bwd_args 
             res_barrier();
             STAMP(6);
             tile_rows_to_global<GH>(dabuf, da_rows, w, l);
-#ifndef BF_
-#define BF_(ks) bfrag(ks)
-#endif
             RES_PHASE(acc[0], acc[1], acc[2], acc[3], 0, 2 * SH, BF_, RES_NOHOOK);
 #pragma unroll
             for (int n = 0; n < RNT; ++n)
@@ -1585,6 +1420,10 @@ __global__ __launch_bounds__(256, 1) void rnn_bwd_res_k(const mvae_rnn_bwd_args 
 //             E, and a whole M phase - more than an HBM round trip - passes before the next E needs them)
 // Fragment classes in order of use: T (first k-group; streamed from L2 during E into the registers that stage
 // LDS-resident fragments during M), A accumulator registers, V vector registers, L LDS.
+// Filler slots (profiles/r03_r_bptt_slots.txt): the write-through da stores as LATE as the staging registers allow - slots 16..
+// cost +0.33 ms per train step, 44 +0.03, 50 (round 2) 0, 58 -0.05: stores in flight slow the return of the next step's
+// prefetched values more than their acknowledgement is missed at the T-fragment drain
+constexpr int BWL_LOAD_STRIDE = 3, BWL_COPY_SLOT = 58, BWL_COPY_STRIDE = 4;
 template <bool HAS_EXT, int NA, int NV>
 __device__ __forceinline__ void lstm_bwd_il_body(const mvae_rnn_bwd_args& a, const unsigned bx) {
     constexpr int G = 4, GH = G * RH, S2 = GH / 32, FPW = RNT * S2;
@@ -1637,13 +1476,8 @@ __device__ __forceinline__ void lstm_bwd_il_body(const mvae_rnn_bwd_args& a, con
     // wave-uniform running pointers for step t-1 (the step whose values are fetched during step t)
     gbyte *acts_p[G], *cs_p, *dx_p, *da_p;
     const size_t dx_step = tps * (RH / 16) * 512, da_step = (size_t)B * GH * 2;
-#if RES_WGMAJOR
-    const size_t acts_step = (size_t)(GH / 32) * 1024, cs_step = (size_t)(RH / 32) * 1024;
-    const size_t acts_bT = ((size_t)bx * T + (T - 1)) * (GH / 32), cs_bT = ((size_t)bx * (T + 1) + (T - 1)) * (RH / 32);
-#else
     const size_t acts_step = tps * (GH / 16) * 512, cs_step = dx_step;
     const size_t acts_bT = ((size_t)(T - 1) * tps + bx) * (GH / 32), cs_bT = ((size_t)(T - 1) * tps + bx) * (RH / 32);
-#endif
 #pragma unroll
     for (int g = 0; g < G; ++g)
         acts_p[g] = to_global(a.acts) + (acts_bT + g * (RH / 32) + w * 2) * 1024;
@@ -1680,7 +1514,6 @@ __device__ __forceinline__ void lstm_bwd_il_body(const mvae_rnn_bwd_args& a, con
     dx_p -= (T > 1 ? dx_step : 0);
 
     float fillr = 0.f; (void)fillr;      // (ABL_FILL probe)
-    const s16x4 ident = identity_fragment(l);
     frag bq[2], lt[4];      // B fragments: one k-group ahead (a third ring slot costs 4 registers this kernel lacks)
     vm_drain();
     lds_barrier();
@@ -1696,7 +1529,6 @@ __device__ __forceinline__ void lstm_bwd_il_body(const mvae_rnn_bwd_args& a, con
         if (HAS_EXT) wave_wait_ge_if(t, pwait, a.wait_ready + (pk - 1), wait_value, a.status, 2u);
         // ---- E: everything requested during the previous M phase has had that whole phase to arrive (the compiler's
         // counted waits for the loads; no drain: the da stores issued at the end of that phase may still be in flight)
-        if (GB_DRAIN) vm_drain();
         STAMP(1);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -1713,33 +1545,24 @@ __device__ __forceinline__ void lstm_bwd_il_body(const mvae_rnn_bwd_args& a, con
         for (int n = 0; n < RNT; ++n) {
             auto half = [&](const u16x8& v) -> f32x4 {
                 const int o = (n & 1) * 4;
-                if (BWL_MFMA_WIDEN > 1)
-                    return widen4(ident, (n & 1) ? __builtin_shufflevector(v, v, 4, 5, 6, 7) : __builtin_shufflevector(v, v, 0, 1, 2, 3),
-                                  f32x4{0.f, 0.f, 0.f, 0.f});
                 return f32x4{bf2f(v[o]), bf2f(v[o + 1]), bf2f(v[o + 2]), bf2f(v[o + 3])};
             };
             const f32x4 ig = half(qa[n >> 1][0]), fg = half(qa[n >> 1][1]), gg = half(qa[n >> 1][2]), og = half(qa[n >> 1][3]);
             const f32x4 c = half(carry[n >> 1]), cp = half(qs[n >> 1]);
             f32x4 d = dh[n];
-            if (HAS_EXT) d = BWL_MFMA_WIDEN ? widen4(ident, qd[n], d) : d + unpack4(qd[n]);
+            if (HAS_EXT) d = d + unpack4(qd[n]);
             // whole-vector expressions: no MFMA is in flight in this phase, so packed f32 instructions (two elements
             // each) are pure gain here - unlike in the MFMA gaps, where they cost issue slots
             f32x4 di, df, dg, dO;
             if (ABL_NOMATH) { di = d; df = d; dg = d; dO = d; dc[n] = d; }     // (timing ablation: the E phase without its arithmetic)
             else {
                 const f32x4 tc = tanh_fast4(c);
-                const f32x4 dct = dc[n] + d * og * (BWL_ASM_1MSQ ? one_minus_sq4(tc) : 1.0f - tc * tc);
-#if BWL_OLD_DHS
-                di = dct * (gg * dhard_sigmoid4(ig));
-                df = dct * (cp * dhard_sigmoid4(fg));
-                dO = d * (tc * dhard_sigmoid4(og));
-#else
+                const f32x4 dct = dc[n] + d * og * one_minus_sq4(tc);
                 const f32x4 dctK = dct * DHS_BIG, dK = d * DHS_BIG;       // (powers of two: exact; |dct| < 2^27 or the step is lost anyway)
                 di = (dctK * gg) * sat4(ig);
                 df = (dctK * cp) * sat4(fg);
                 dO = (dK * tc) * sat4(og);
-#endif
-                dg = dct * ig * (BWL_ASM_1MSQ ? one_minus_sq4(gg) : 1.0f - gg * gg);
+                dg = dct * ig * one_minus_sq4(gg);
                 dc[n] = dct * fg;
             }
             // (da0's 16-byte chunk index is < 32: the gate's 512 bytes never meet a set bit, so they are an instruction immediate
@@ -1750,35 +1573,24 @@ __device__ __forceinline__ void lstm_bwd_il_body(const mvae_rnn_bwd_args& a, con
             *reinterpret_cast<u16x4*>(dan + 2 * 512) = pack4(dg);
             *reinterpret_cast<u16x4*>(dan + 3 * 512) = pack4(dO);
             if (n & 1) carry[n >> 1] = qs[n >> 1];      // c_{t-1} is the next step's c_t
-#if BWL_E_TILE_FENCE
-            __builtin_amdgcn_sched_barrier(0);
-#endif
         }
         STAMP(2);
         vm_drain();                                   // the T fragments (L2 hits issued a whole E phase ago)
         pinq(lt[0]); pinq(lt[1]); pinq(lt[2]); pinq(lt[3]);
         if (ABL_NOBAR1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); else res_barrier();
-        res_skew(w);
         STAMP(3);
 
         // ---- M -------------------------------------------------------------------------------------------------
         f32x4 acc[RNT];
-#if !BWL_MFMA_FIRST
 #pragma unroll
         for (int n = 0; n < RNT; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
-#endif
         bq[0] = *reinterpret_cast<const frag*>(dabuf + bb0);
         static_for<0, FPW>(SF_LAMBDA(sc) {
             constexpr int sl = decltype(sc)::value, gi = sl >> 2, n = sl & 3, ci = sl - NT;
             if constexpr (n == 0 && gi + 1 < S2 && !(ABL_NOB && gi >= 1))
                 bq[(gi + 1) & 1] = *reinterpret_cast<const frag*>(dabuf + (bb0 ^ (((gi + 1) & 3) << 6)) + 256 * ((gi + 1) >> 2));
-#if BWL_MFMA_FIRST
-            if constexpr (sl == 0) asm volatile("s_nop 1");
-            if constexpr (sl < NT) mfma1_first(acc[n], lt[n], bq[gi & 1]);       // (the accumulators start here: C = 0 inline)
-#else
             if constexpr (sl == 0) asm volatile("s_nop 1" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]));
             if constexpr (sl < NT) mfma1<false>(acc[n], lt[n], bq[gi & 1]);
-#endif
             else if constexpr (ci < NA) mfma1<true>(acc[n], ua[ci < NA ? ci : 0], bq[gi & 1]);
             else if constexpr (ci < NA + NV) mfma1<false>(acc[n], uv[(ci >= NA && ci < NA + NV) ? ci - NA : 0], bq[gi & 1]);
             else mfma1<false>(acc[n], lt[n], bq[gi & 1]);
@@ -1867,15 +1679,7 @@ __global__ __launch_bounds__(256, 1) void lstm_bwd_il_k(const mvae_rnn_bwd_args 
 // 64 + 32 fragments per wave: accumulator registers + LDS (24 KiB da tile + 8 KiB rh tile + 128 KiB = all of it).
 // A memory instruction occupies the CU's address unit for ~27 cycles whatever its width (4 waves: ~108 cycles per wave
 // and instruction), hence 16-byte accesses wherever the layout allows: acts TILE16P, copies in 16-byte chunks.
-#ifndef GB_NOLOAD
-#define GB_NOLOAD 0
-#endif
-#ifndef GB_NOCOPY
-#define GB_NOCOPY 0
-#endif
-#ifndef GB_NODAZ
-#define GB_NODAZ 0
-#endif
+// (GB_NOLOAD / GB_NOCOPY / GB_NODAZ: timing ablations, ablations.h)
 template <bool HAS_EXT>
 __device__ __forceinline__ void gru_bwd_il_body(const mvae_rnn_bwd_args& a, const unsigned bx) {
     constexpr int G = 3, GH = G * RH, S2 = GH / 32, NLc = RNT * (RH / 32);      // 24 k-groups; 32 LDS fragments per wave
@@ -2031,7 +1835,7 @@ __device__ __forceinline__ void gru_bwd_il_body(const mvae_rnn_bwd_args& a, cons
         STAMP(0);
         // pipelined stack: the upstream gradient of step t-1 is requested during this step's MFMA phases
         if (HAS_EXT) wave_wait_ge_if(t, __builtin_amdgcn_readfirstlane(pwait), uniform_ptr(a.wait_ready + (pk - 1)), wait_value, a.status, 2u);
-        if (GB_DRAIN) vm_drain();       // (else the compiler's counted waits: the copy stores of M2 may still be in flight)
+        // (no drain - the compiler's counted waits: the copy stores of M2 may still be in flight)
         STAMP(1);
         pinq(qr[0]); pinq(qr[1]);
         if (HAS_EXT) {
@@ -2192,37 +1996,18 @@ __global__ __launch_bounds__(256, 1) void gru_bwd_il_k(const mvae_rnn_bwd_args a
 // dispatch
 // ---------------------------------------------------------------------------------------------------------
 // fragment placement per kernel: A in accumulator registers, V in vector registers, the rest in LDS (per wave)
-#ifndef RES_LSTM_FA
-#define RES_LSTM_IA 64
-#define RES_LSTM_IV 24
-#define RES_LSTM_JA 64
-#define RES_LSTM_JV 28
-#define RES_LSTM_FA 64
-#define RES_LSTM_FV 28
-#define RES_LSTM_FVS 32
-#define RES_LSTM_BA 64
-#define RES_LSTM_BV 32
-#define RES_GRU_FA 64
-#define RES_GRU_FV 8
-#define RES_GRU_BA 64
-#define RES_GRU_BV 8
-#endif
-#ifndef RES_LSTM_PIPELINE
-#define RES_LSTM_PIPELINE 1
-#endif
-
 template <int CELL> struct res_cfg;
 template <> struct res_cfg<MVAE_LSTM> {   // 128 fragments per wave
-    static constexpr int IA = RES_LSTM_IA, IV = RES_LSTM_IV;     // slot-interleaved forward (+4 streamed, rest LDS)
-    static constexpr int JA = RES_LSTM_JA, JV = RES_LSTM_JV;     // slot-interleaved backward (+4 streamed, 32 LDS)
-    static constexpr int FA = RES_LSTM_FA, FV = RES_LSTM_FV;     // rest in LDS (16 KiB h tiles + <= 144 KiB)
-    static constexpr int FV_SCALAR = RES_LSTM_FVS;               // 8 KiB of LDS go to the scalar-input weights
-    static constexpr int BA = RES_LSTM_BA, BV = RES_LSTM_BV;     // rest in LDS (32 KiB da tile + <= 128 KiB)
+    static constexpr int IA = 64, IV = 24;     // slot-interleaved forward (+4 streamed, rest LDS)
+    static constexpr int JA = 64, JV = 28;     // slot-interleaved backward (+4 streamed, 32 LDS)
+    static constexpr int FA = 64, FV = 28;     // rest in LDS (16 KiB h tiles + <= 144 KiB)
+    static constexpr int FV_SCALAR = 32;               // 8 KiB of LDS go to the scalar-input weights
+    static constexpr int BA = 64, BV = 32;     // rest in LDS (32 KiB da tile + <= 128 KiB)
 };
 template <> struct res_cfg<MVAE_GRU> {    // 96 fragments per wave
-    static constexpr int FA = RES_GRU_FA, FV = RES_GRU_FV;
-    static constexpr int FV_SCALAR = RES_GRU_FV;
-    static constexpr int BA = RES_GRU_BA, BV = RES_GRU_BV;
+    static constexpr int FA = 64, FV = 8;
+    static constexpr int FV_SCALAR = 8;
+    static constexpr int BA = 64, BV = 8;
 };
 
 template <int CELL, int XMODE, int SAVE>
@@ -2232,16 +2017,7 @@ int launch_fwd_res(const mvae_rnn_fwd_args& a, hipStream_t s) {
     constexpr int G = mvae_gates(CELL), NL = G * RNT * RS - C::FA - FVx;
     const size_t lds = (size_t)(2 + (CELL == MVAE_GRU ? 1 : 0)) * 16 * RH * sizeof(bf16_t) +
                        (size_t)4 * NL * 64 * sizeof(frag) + (XMODE == MVAE_X_SCALAR ? (size_t)2 * G * RH * sizeof(float) : 0);
-    static bool raised = false;
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&rnn_fwd_res_k<CELL, XMODE, SAVE, C::FA, FVx>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return MVAE_E_LAUNCH;
-        raised = true;
-    }
-    hipLaunchKernelGGL((rnn_fwd_res_k<CELL, XMODE, SAVE, C::FA, FVx>), dim3(a.B / 16), dim3(256), lds, s, a);
-    MVAE_CHECK_LAUNCH();
-    return MVAE_OK;
+    return mvae_launch<rnn_fwd_res_k<CELL, XMODE, SAVE, C::FA, FVx>>(dim3(a.B / 16), dim3(256), lds, s, a);
 }
 // LSTM with dense / indexed / constant inputs and seq_layout TILE16P: the slot-interleaved kernel
 template <int XMODE, int SAVE>
@@ -2249,32 +2025,14 @@ int launch_lstm_il(const mvae_rnn_fwd_args& a, hipStream_t s) {
     typedef res_cfg<MVAE_LSTM> C;
     constexpr int NL = 4 * RNT * RS - 4 - C::IA - C::IV;
     const size_t lds = (size_t)2 * 16 * RH * sizeof(bf16_t) + (size_t)4 * NL * 64 * sizeof(frag);
-    static bool raised = false;
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_fwd_il_k<XMODE, SAVE, C::IA, C::IV>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return MVAE_E_LAUNCH;
-        raised = true;
-    }
-    hipLaunchKernelGGL((lstm_fwd_il_k<XMODE, SAVE, C::IA, C::IV>), dim3(a.B / 16), dim3(256), lds, s, a);
-    MVAE_CHECK_LAUNCH();
-    return MVAE_OK;
+    return mvae_launch<lstm_fwd_il_k<XMODE, SAVE, C::IA, C::IV>>(dim3(a.B / 16), dim3(256), lds, s, a);
 }
 
 // GRU with dense / indexed / constant inputs and seq_layout TILE16P: the slot-interleaved kernel
 template <int XMODE, int SAVE>
 int launch_gru_il(const mvae_rnn_fwd_args& a, hipStream_t s) {
     const size_t lds = (size_t)3 * 16 * RH * sizeof(bf16_t) + (size_t)4 * RNT * RS * 64 * sizeof(frag);
-    static bool raised = false;
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gru_fwd_il_k<XMODE, SAVE>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return MVAE_E_LAUNCH;
-        raised = true;
-    }
-    hipLaunchKernelGGL((gru_fwd_il_k<XMODE, SAVE>), dim3(a.B / 16), dim3(256), lds, s, a);
-    MVAE_CHECK_LAUNCH();
-    return MVAE_OK;
+    return mvae_launch<gru_fwd_il_k<XMODE, SAVE>>(dim3(a.B / 16), dim3(256), lds, s, a);
 }
 template <int CELL, int XMODE>
 int fwd_res_save(const mvae_rnn_fwd_args& a, hipStream_t s) {
@@ -2315,31 +2073,13 @@ int launch_lstm_bwd_il(const mvae_rnn_bwd_args& a, hipStream_t s) {
     typedef res_cfg<MVAE_LSTM> C;
     constexpr int NL = RNT * (4 * RH / 32) - 4 - C::JA - C::JV;
     const size_t lds = (size_t)16 * 4 * RH * sizeof(bf16_t) + (size_t)4 * NL * 64 * sizeof(frag);
-    static bool raised = false;
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_bwd_il_k<HAS_EXT, C::JA, C::JV>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return MVAE_E_LAUNCH;
-        raised = true;
-    }
-    hipLaunchKernelGGL((lstm_bwd_il_k<HAS_EXT, C::JA, C::JV>), dim3(a.B / 16), dim3(256), lds, s, a);
-    MVAE_CHECK_LAUNCH();
-    return MVAE_OK;
+    return mvae_launch<lstm_bwd_il_k<HAS_EXT, C::JA, C::JV>>(dim3(a.B / 16), dim3(256), lds, s, a);
 }
 template <bool HAS_EXT>
 int launch_gru_bwd_il(const mvae_rnn_bwd_args& a, hipStream_t s) {
     const size_t lds = (size_t)16 * 3 * RH * sizeof(bf16_t) + (size_t)16 * RH * sizeof(bf16_t) +
                        (size_t)4 * RNT * (RH / 32) * 64 * sizeof(frag);
-    static bool raised = false;
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gru_bwd_il_k<HAS_EXT>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return MVAE_E_LAUNCH;
-        raised = true;
-    }
-    hipLaunchKernelGGL((gru_bwd_il_k<HAS_EXT>), dim3(a.B / 16), dim3(256), lds, s, a);
-    MVAE_CHECK_LAUNCH();
-    return MVAE_OK;
+    return mvae_launch<gru_bwd_il_k<HAS_EXT>>(dim3(a.B / 16), dim3(256), lds, s, a);
 }
 template <int CELL, bool HAS_EXT>
 int launch_bwd_res(const mvae_rnn_bwd_args& a, hipStream_t s) {
@@ -2352,16 +2092,7 @@ int launch_bwd_res(const mvae_rnn_bwd_args& a, hipStream_t s) {
     constexpr int G = mvae_gates(CELL), NL = RNT * (G * RH / 32) - C::BA - C::BV;
     const size_t lds = (size_t)16 * G * RH * sizeof(bf16_t) + (size_t)4 * NL * 64 * sizeof(frag) +
                        (CELL == MVAE_GRU ? (size_t)16 * RH * sizeof(bf16_t) : 0);
-    static bool raised = false;
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&rnn_bwd_res_k<CELL, HAS_EXT, C::BA, C::BV>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return MVAE_E_LAUNCH;
-        raised = true;
-    }
-    hipLaunchKernelGGL((rnn_bwd_res_k<CELL, HAS_EXT, C::BA, C::BV>), dim3(a.B / 16), dim3(256), lds, s, a);
-    MVAE_CHECK_LAUNCH();
-    return MVAE_OK;
+    return mvae_launch<rnn_bwd_res_k<CELL, HAS_EXT, C::BA, C::BV>>(dim3(a.B / 16), dim3(256), lds, s, a);
 }
 
 
@@ -2426,16 +2157,7 @@ int launch_fwd_multi(const rnn_fwd_multi& m, int total, hipStream_t s) {
     constexpr int NL = 4 * RNT * RS - 4 - C::IA - C::IV;
     const size_t lds = CELL == MVAE_LSTM ? (size_t)2 * 16 * RH * sizeof(bf16_t) + (size_t)4 * NL * 64 * sizeof(frag)
                                          : (size_t)3 * 16 * RH * sizeof(bf16_t) + (size_t)4 * RNT * RS * 64 * sizeof(frag);
-    static bool raised = false;
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&rnn_fwd_multi_k<CELL, SAVE>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess)
-            return MVAE_E_LAUNCH;
-        raised = true;
-    }
-    hipLaunchKernelGGL((rnn_fwd_multi_k<CELL, SAVE>), dim3(total), dim3(256), lds, s, m);
-    MVAE_CHECK_LAUNCH();
-    return MVAE_OK;
+    return mvae_launch<rnn_fwd_multi_k<CELL, SAVE>>(dim3(total), dim3(256), lds, s, m);
 }
 template <int CELL>
 int launch_bwd_multi(const rnn_bwd_multi& m, int total, hipStream_t s) {
@@ -2444,16 +2166,7 @@ int launch_bwd_multi(const rnn_bwd_multi& m, int total, hipStream_t s) {
     const size_t lds = CELL == MVAE_LSTM ? (size_t)16 * 4 * RH * sizeof(bf16_t) + (size_t)4 * NL * 64 * sizeof(frag)
                                          : (size_t)16 * 3 * RH * sizeof(bf16_t) + (size_t)16 * RH * sizeof(bf16_t) +
                                                (size_t)4 * RNT * (RH / 32) * 64 * sizeof(frag);
-    static bool raised = false;
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&rnn_bwd_multi_k<CELL>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess)
-            return MVAE_E_LAUNCH;
-        raised = true;
-    }
-    hipLaunchKernelGGL((rnn_bwd_multi_k<CELL>), dim3(total), dim3(256), lds, s, m);
-    MVAE_CHECK_LAUNCH();
-    return MVAE_OK;
+    return mvae_launch<rnn_bwd_multi_k<CELL>>(dim3(total), dim3(256), lds, s, m);
 }
 
 }  // namespace

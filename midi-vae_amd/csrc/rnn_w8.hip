@@ -18,48 +18,12 @@
 // LSTM BPTT (lstm_bwd_w8_k, MVAE_LSTM_BWD_W8=1, NOT the product): U^T is 512 KiB = the whole register file; a quarter of it streams
 // from L2 every step and queues behind the HBM requests of the next step's saved activations: 3.9 vs 2.7 us per step
 // (profiles/r06_g_lstm_bptt_w8.txt).  Kept with its parity test because the finding is the kernel.
-#include "common.h"
+#include "rnn_res_common.h"
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
 
-// Development switches (variant builds only: tools/build_w8_variants.sh; every W8_ABL_* makes the results WRONG)
-#ifndef W8_ABL_NOBAR
-#define W8_ABL_NOBAR 0      /* no barriers */
-#endif
-#ifndef W8_ABL_NOMATH
-#define W8_ABL_NOMATH 0     /* no gate arithmetic */
-#endif
-#ifndef W8_ABL_NOL
-#define W8_ABL_NOL 0        /* LDS-resident weight fragments replaced by register ones */
-#endif
-#ifndef W8_ABL_NOB
-#define W8_ABL_NOB 0        /* B fragments read once per launch */
-#endif
-#ifndef W8_B2B
-#define W8_B2B 13           /* GRU forward: slot behind which barrier 2b stands (the h_b write is slot 6; h_b is needed from slot 16) */
-#endif
-#ifndef W8_B1
-#define W8_B1 30            /* ... barrier 1 (the last r*h write is slot 27; r*h is needed from slot 32) */
-#endif
-#ifndef W8_TA0
-#define W8_TA0 42           /* ... first slot of tile a's tanh + h update (3 slots, then the h_a write; its last MFMA is slot 39) */
-#endif
-#ifndef W8_BWD_Z_LATE
-#define W8_BWD_Z_LATE 0     /* GRU BPTT: da_z (only M2z waits for it, slot 16) computed behind barrier 1 and exchanged by a barrier of its own in slot 8 */
-#endif
-#ifndef W8_ABL_NOSTREAM
-#define W8_ABL_NOSTREAM 0   /* LSTM BPTT: the fragments streamed from L2 replaced by register ones (no requests) */
-#endif
-#ifndef W8_ABL_NOLOADS
-#define W8_ABL_NOLOADS 0    /* LSTM BPTT: no requests of the next step's saved values (the stream alone in the memory queue) */
-#endif
-#ifndef W8_PRIO
-#define W8_PRIO 0           /* s_setprio 1 for waves 4..7 (the second-dispatched wave of every SIMD) */
-#endif
-#ifndef MVAE_VARIANT_BUILD
-static_assert(!W8_ABL_NOBAR && !W8_ABL_NOMATH && !W8_ABL_NOL && !W8_ABL_NOB && !W8_ABL_NOSTREAM && !W8_ABL_NOLOADS, "timing ablations: variant builds only");
-#endif
+#include "ablations.h"      // W8_ABL_* timing switches: all 0 in the product build (variant builds only: tools/build_w8_variants.sh)
 
 // Phase stamps (build with -DW8_STAMPS): lane 0 of waves 0 and 4 of block 0 records s_memtime at marked points of steps
 // [64, 72); read back with mvae_debug_stamps_w8().  Development tooling only.
@@ -80,29 +44,9 @@ extern "C" int mvae_debug_stamps_w8(unsigned long long* out) {
 namespace {
 
 constexpr int RH = 256;
-typedef u16x8 frag;
-typedef __attribute__((address_space(1))) unsigned char gbyte;
-typedef __attribute__((address_space(1))) u16x4 g_u16x4;
-typedef __attribute__((address_space(1))) u16x8 g_u16x8;
-enum { SAVE_NONE = 0, SAVE_HS = 1, SAVE_ALL = 2 };
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-#define SF_LAMBDA(ic) [&](auto ic) __attribute__((always_inline))
-template <bool AG>
-__device__ __forceinline__ void mfma1(f32x4& c, const frag& u, const frag& b) {
-    if (AG) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c) : "a"(u), "v"(b));
-    else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(u), "v"(b));
-}
 __device__ __forceinline__ void load1_agpr_nowait(frag& u, const frag* p) {
     asm volatile("global_load_dwordx4 %0, %1, off" : "=&a"(u) : "v"(p) : "memory");
 }
-__device__ __forceinline__ void vm_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 template <int N>
 __device__ __forceinline__ void vm_wait() {
     static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field");
@@ -119,26 +63,6 @@ __device__ __forceinline__ void pin8(u16x8& a) { asm volatile("" : "+v"(a)); }
 __device__ __forceinline__ void iload1(int& d, const uint8_t* p) {
     asm volatile("global_load_ubyte %0, %1, off" : "=v"(d) : "v"(p) : "memory");
 }
-__device__ __forceinline__ void pinu(unsigned& v) { asm volatile("" : "+v"(v)); }
-__device__ __forceinline__ void pini(int& v) { asm volatile("" : "+v"(v)); }
-__device__ __forceinline__ void pin1(u16x4& a) { asm volatile("" : "+v"(a)); }
-__device__ __forceinline__ void pins(gbyte*& p) { asm volatile("" : "+s"(p)); }
-__device__ __forceinline__ gbyte* to_global(const void* p) { return (gbyte*)(const_cast<void*>(p)); }
-__device__ __forceinline__ void store16_wt(gbyte* uniform_base, unsigned lane_off, u16x8 v) {
-    ::store16_wt((const void*)uniform_base, lane_off, v);
-}
-template <typename T>
-__device__ __forceinline__ T* uniform_ptr(T* p) {
-    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return reinterpret_cast<T*>(((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ f32x4 unpack4(u16x4 p) { return f32x4{bf2f(p[0]), bf2f(p[1]), bf2f(p[2]), bf2f(p[3])}; }
-__device__ __forceinline__ u16x4 pack4(f32x4 v) {
-    typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-    return __builtin_bit_cast(u16x4, __builtin_convertvector(v, bf16x4));
-}
-__device__ __forceinline__ u16x8 cat8(u16x4 a, u16x4 b) { return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7); }
 __device__ __forceinline__ void w8_barrier() {
     if (W8_ABL_NOBAR) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     else lds_barrier();
@@ -177,6 +101,9 @@ __host__ __device__ constexpr w8_slot gru_slot(int s) {
 // 16 of the 48 fragments of a wave live in LDS (every third slot), 32 in accumulator registers
 __host__ __device__ constexpr bool gru_is_l(int s) { return s % 3 == 2; }
 __host__ __device__ constexpr int gru_lidx(int s) { return s / 3; }
+constexpr int W8_B2B = 13;      // slot behind which barrier 2b stands (the h_b write is slot 6; h_b is needed from slot 16)
+constexpr int W8_B1 = 30;       // ... barrier 1 (the last r*h write is slot 27; r*h is needed from slot 32)
+constexpr int W8_TA0 = 42;      // ... first slot of tile a's tanh + h update (3 slots, then the h_a write; its last MFMA is slot 39)
 
 template <int XMODE, int SAVE>
 __device__ __forceinline__ void gru_fwd_w8_body(const mvae_rnn_fwd_args& a, const unsigned bx) {
@@ -315,7 +242,6 @@ __device__ __forceinline__ void gru_fwd_w8_body(const mvae_rnn_fwd_args& a, cons
     frag bh[8], lt[2], cp;     // B fragments: h k-groups 0..7, then (dead registers first) r*h: 0..3 behind barrier 1, 4..7 behind slot 31
     vm_drain();
     lds_barrier();
-    if (W8_PRIO && w >= 4) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) bh[ks] = *reinterpret_cast<const frag*>(hbuf + bf4[ks]);
 #pragma unroll
@@ -730,10 +656,10 @@ __device__ __forceinline__ void gru_bwd_w8_body(const mvae_rnn_bwd_args& a, cons
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 dac[e] = d[n][e] * w1[n][e];
-                if (!W8_BWD_Z_LATE) daz[e] = d[n][e] * kz[n][e];
+                daz[e] = d[n][e] * kz[n][e];
             }
             *reinterpret_cast<u16x4*>(dabuf + (da_w0 + (2 * 512 + n * 256))) = pack4(dac);
-            if (!W8_BWD_Z_LATE) *reinterpret_cast<u16x4*>(dabuf + (da_w0 + (0 * 512 + n * 256))) = pack4(daz);
+            *reinterpret_cast<u16x4*>(dabuf + (da_w0 + (0 * 512 + n * 256))) = pack4(daz);
         }
         w8_barrier();                                                     // ---- 1: da_c, da_z
         bq[0] = *reinterpret_cast<const frag*>(dabuf + b_row + (b_ch ^ (16u << 6)));
@@ -770,14 +696,6 @@ __device__ __forceinline__ void gru_bwd_w8_body(const mvae_rnn_bwd_args& a, cons
             // (requests are unconditional - at t = 0 step 0's values once more: a request under a branch is an asm output merged
             //  with the old value behind it, i.e. a register copy of data that has not landed)
             if constexpr (sl == 0) issue_early(0, 0);                     // (acts_p / hs_p / dx_p were moved to step t-1 above)
-            if constexpr (W8_BWD_Z_LATE && (sl == 2 || sl == 4)) {
-                constexpr int n = sl == 4;
-                f32x4 daz;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) daz[e] = d[n][e] * kz[n][e];
-                *reinterpret_cast<u16x4*>(dabuf + (da_w0 + (0 * 512 + n * 256))) = pack4(daz);
-            }
-            if constexpr (W8_BWD_Z_LATE && sl == 9) w8_barrier();          // ---- 1b: da_z (its first B fragment is requested in slot 12)
             // M2's accumulators start at d z
             if constexpr (sl == 10 || sl == 12) {
                 constexpr int n = sl == 12;
@@ -891,16 +809,7 @@ __global__ __launch_bounds__(512, 1) void gru_bwd_w8_k(const mvae_rnn_bwd_args a
 template <bool HAS_EXT>
 int launch_gru_bwd_w8(const mvae_rnn_bwd_args& a, hipStream_t s) {
     const size_t lds = (size_t)16 * 3 * RH * sizeof(bf16_t) + (size_t)16 * RH * sizeof(bf16_t) + (size_t)8 * 16 * 64 * sizeof(frag);
-    static bool raised = false;
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gru_bwd_w8_k<HAS_EXT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess)
-            return MVAE_E_LAUNCH;
-        raised = true;
-    }
-    hipLaunchKernelGGL((gru_bwd_w8_k<HAS_EXT>), dim3(a.B / 16), dim3(512), lds, s, a);
-    MVAE_CHECK_LAUNCH();
-    return MVAE_OK;
+    return mvae_launch<gru_bwd_w8_k<HAS_EXT>>(dim3(a.B / 16), dim3(512), lds, s, a);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1211,16 +1120,7 @@ __global__ __launch_bounds__(512, 1) void lstm_bwd_w8_k(const mvae_rnn_bwd_args 
 template <bool HAS_EXT>
 int launch_lstm_bwd_w8(const mvae_rnn_bwd_args& a, hipStream_t s) {
     const size_t lds = (size_t)16 * 4 * RH * sizeof(bf16_t) + (size_t)8 * 16 * 64 * sizeof(frag);
-    static bool raised = false;
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_bwd_w8_k<HAS_EXT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess)
-            return MVAE_E_LAUNCH;
-        raised = true;
-    }
-    hipLaunchKernelGGL((lstm_bwd_w8_k<HAS_EXT>), dim3(a.B / 16), dim3(512), lds, s, a);
-    MVAE_CHECK_LAUNCH();
-    return MVAE_OK;
+    return mvae_launch<lstm_bwd_w8_k<HAS_EXT>>(dim3(a.B / 16), dim3(512), lds, s, a);
 }
 
 constexpr int GRU_W8_NLDS = 16;
@@ -1232,16 +1132,7 @@ __global__ __launch_bounds__(512, 1) void gru_fwd_w8_k(const mvae_rnn_fwd_args a
 template <int XMODE, int SAVE>
 int launch_gru_w8(const mvae_rnn_fwd_args& a, hipStream_t s) {
     const size_t lds = (size_t)3 * 16 * RH * sizeof(bf16_t) + (size_t)8 * GRU_W8_NLDS * 64 * sizeof(frag);
-    static bool raised = false;
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gru_fwd_w8_k<XMODE, SAVE>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return MVAE_E_LAUNCH;
-        raised = true;
-    }
-    hipLaunchKernelGGL((gru_fwd_w8_k<XMODE, SAVE>), dim3(a.B / 16), dim3(512), lds, s, a);
-    MVAE_CHECK_LAUNCH();
-    return MVAE_OK;
+    return mvae_launch<gru_fwd_w8_k<XMODE, SAVE>>(dim3(a.B / 16), dim3(512), lds, s, a);
 }
 template <int XMODE>
 int gru_w8_save(const mvae_rnn_fwd_args& a, hipStream_t s) {
@@ -1284,16 +1175,7 @@ __global__ __launch_bounds__(512, 1) void gru_bwd_multi_w8_k(const rnn_bwd_multi
 template <int SAVE>
 int launch_fwd_multi_w8(const rnn_fwd_multi& m, int total, hipStream_t s) {
     const size_t lds = (size_t)3 * 16 * RH * sizeof(bf16_t) + (size_t)8 * GRU_W8_NLDS * 64 * sizeof(frag);
-    static bool raised = false;
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gru_fwd_multi_w8_k<SAVE>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess)
-            return MVAE_E_LAUNCH;
-        raised = true;
-    }
-    hipLaunchKernelGGL((gru_fwd_multi_w8_k<SAVE>), dim3(total), dim3(512), lds, s, m);
-    MVAE_CHECK_LAUNCH();
-    return MVAE_OK;
+    return mvae_launch<gru_fwd_multi_w8_k<SAVE>>(dim3(total), dim3(512), lds, s, m);
 }
 
 }  // namespace
@@ -1377,14 +1259,5 @@ int mvae_rnn_bwd_multi_w8(const mvae_rnn_bwd_args* problems, int32_t n, void* st
     m.base[n] = total;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const size_t lds = (size_t)16 * 3 * RH * sizeof(bf16_t) + (size_t)16 * RH * sizeof(bf16_t) + (size_t)8 * 16 * 64 * sizeof(frag);
-    static bool raised = false;
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gru_bwd_multi_w8_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-            hipSuccess)
-            return MVAE_E_LAUNCH;
-        raised = true;
-    }
-    hipLaunchKernelGGL(gru_bwd_multi_w8_k, dim3(total), dim3(512), lds, s, m);
-    MVAE_CHECK_LAUNCH();
-    return MVAE_OK;
+    return mvae_launch<gru_bwd_multi_w8_k>(dim3(total), dim3(512), lds, s, m);
 }

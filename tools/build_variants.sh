@@ -1,5 +1,5 @@
 #!/bin/bash
-# Development: build timing variants of the resident recurrent kernels (ablations / register configs) next to the
+# Development: build timing variants of the resident recurrent kernels (ablations) next to the
 # product library, for tools/rnn_microbench.py via MVAE_LIB.   tools/build_variants.sh name1:"-DFLAG=1 ..." name2:...
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
