@@ -111,10 +111,14 @@ typedef struct {
      * words in device memory, zeroed by the caller before the launches.  Every producer stores the data it hands over
      * WRITE-THROUGH (sc1) and publishes behind a drained vmcnt - no L2 write-back: a buffer_wbl2 per hand-over writes back
      * the whole XCD's L2 and stalls the recurrent workgroups that share it (7.5 % of a training step). */
-    int32_t chunk_steps;         /* time steps per pipeline chunk; chunk k = steps [k*chunk_steps, (k+1)*chunk_steps)    */
+    int32_t chunk_steps;         /* time steps per pipeline chunk; chunk k = steps [k*chunk_steps, (k+1)*chunk_steps).
+                                    With wait_ready it must be >= 2 (1: MVAE_E_ARG, also from mvae_rnn_fwd_multi): the forward
+                                    kernels read xp one or two steps ahead and wait once per chunk.  Publishing alone
+                                    (signal_done) and the backward kernels (mvae_rnn_bwd_args) take 1                      */
     const uint32_t* wait_ready;  /* [chunks] chunk k of xp may be read once wait_ready[k] >= wait_value (kernel polls)    */
     uint32_t wait_value;         /* 0 = 1                                                                                 */
-    uint32_t* signal_done;       /* [chunks] += 1 per WAVE (4 * B/16 of them) once chunk k of hs is complete and visible  */
+    uint32_t* signal_done;       /* [chunks] += mvae_rnn_producer_waves(seq_layout) * B/16 in all (1 per publishing wave) once
+                                    chunk k of hs is complete and visible; needs hs (MVAE_E_ARG without)                   */
     uint32_t* status;            /* [1] set non-zero if a wait timed out (~2-4 s): results are invalid                    */
     int32_t seq_layout;    /* layout of xp, acts and cs (hs is always row-major): MVAE_ROWMAJOR, MVAE_TILE16 or
                               MVAE_TILE16P.  The tiled layouts need B % 16 == 0 and select the resident-weights kernels
@@ -147,7 +151,8 @@ typedef struct {
     int32_t dh_last_ld;    /* row stride of dh_last (0 = H)                                                   */
     int32_t dh0_ld;        /* row stride of dh0 / dc0 (0 = H)                                                 */
     /* time-pipelined stacks, as in mvae_rnn_fwd_args: wait_ready gates dhs_ext (chunk k = steps [k*cs, (k+1)*cs), consumed
-     * from the last chunk to the first), signal_done publishes da */
+     * from the last chunk to the first), signal_done publishes da (and rh): chunk k += mvae_rnn_producer_waves(seq_layout) * B/16 in
+     * all once da of its steps is complete and visible.  chunk_steps may be 1 here */
     int32_t chunk_steps;
     const uint32_t* wait_ready;
     uint32_t wait_value;

@@ -170,7 +170,8 @@ int mvae_launch(dim3 grid, dim3 block, size_t lds, hipStream_t s, const ARGS& ar
 // Single asm blocks with scalar control flow and one or two temporary VGPRs: as C++ (a thread-0 loop, barriers, an
 // atomic) they cost the 256-VGPR LSTM backward kernel registers it does not have, and an extra basic block in its step
 // loop breaks hipcc's allocation.  Every WAVE waits / publishes by itself: no barrier; a counter's consumer expects one
-// increment per producer wave.
+// increment per producer wave - mvae_rnn_producer_waves(seq_layout) per workgroup.  The one exception: lstm_bwd_w8_body (rnn_w8.hip,
+// w8_signal_done_4_of_8_if) runs 8 waves on a TILE16P stack that counts 4: its waves drain their stores, meet at a barrier, 4 publish.
 //
 // wave_wait_ge: until *flag >= value (system-scope loads), then drop this XCD's possibly stale cache lines of the data the
 // flag guards.  Bounded (~2-4 s: a host that stalls in the middle of enqueuing a step must not look like a dead producer): then *status = code (which kind of wait: 1 recurrent forward, 2 BPTT, 3 chunked GEMM, 4 K-streaming GEMM, 5 join) and the kernel carries on - it never hangs.

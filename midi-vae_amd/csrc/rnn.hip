@@ -583,6 +583,9 @@ extern "C" int mvae_rnn_fwd(const mvae_rnn_fwd_args* a, void* stream) {
     if (a->chunk_steps < 0 || ((a->wait_ready || a->signal_done) && a->chunk_steps == 0)) return MVAE_E_ARG;
     if ((a->wait_ready || a->signal_done) && a->seq_layout != MVAE_TILE16P && a->seq_layout != MVAE_TILE16Q) return MVAE_E_UNSUPPORTED;
     if (a->wait_ready && a->xmode != MVAE_X_DENSE) return MVAE_E_ARG;
+    // the forward kernels request their inputs one (LSTM) or two (GRU) steps ahead and wait for a chunk at most once per chunk:
+    // with one-step chunks every step would have to wait, for up to two chunks at once
+    if (a->wait_ready && a->chunk_steps == 1) return MVAE_E_ARG;
     if (a->signal_done && !a->hs) return MVAE_E_ARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (a->H == 256 && a->dtype == MVAE_BF16 && a->cell != MVAE_RNN) {

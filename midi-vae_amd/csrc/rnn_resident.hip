@@ -1009,9 +1009,13 @@ __device__ __forceinline__ void gru_fwd_il_body(const mvae_rnn_fwd_args& a, cons
         const int tstep = t;
         (void)tstep;
         pinu(hw0); pinu(tl0);
-        // pipelined stack: x of step t+2 is requested during this step - its chunk must have been published
-        if (XMODE == MVAE_X_DENSE && cs_steps && a.wait_ready && t + 2 < T && t + 2 == phi)
-            wave_wait_ge(uniform_ptr(a.wait_ready + pk + 1), wait_value, a.status);
+        // pipelined stack: x of step t+2 is requested during this step - its chunk must have been published.  pk / phi move on
+        // at the END of step t == phi (the publish below): in that step the chunk being read ahead of is already pk + 1, ending
+        // before phi + chunk_steps - with chunk_steps == 2 that is the step whose request crosses into the next chunk
+        if (XMODE == MVAE_X_DENSE && cs_steps && a.wait_ready && t + 2 < T) {
+            const int moved = t == phi ? 1 : 0;
+            if (t + 2 == phi + (moved ? cs_steps : 0)) wave_wait_ge(uniform_ptr(a.wait_ready + pk + 1 + moved), wait_value, a.status);
+        }
         pins(acts_p[0]); pins(acts_p[1]); pins(acts_p[2]); pins(hs_p); pins(hh_prev_p);
         pins(x_p[0]); pins(x_p[1]); pins(x_p[2]);
         unsigned char* hcur = hbuf;               // bf4 / tl0 / hw0 carry the buffer bit
@@ -2234,7 +2238,7 @@ extern "C" int mvae_rnn_fwd_multi(const mvae_rnn_fwd_args* problems, int32_t n, 
         const mvae_rnn_fwd_args& a = problems[i];
         if (!a.u_pack || a.T <= 0 || a.B <= 0 || (a.B % 16) || a.chunk_steps < 0 ||
             ((a.wait_ready || a.signal_done) && a.chunk_steps == 0) || (a.wait_ready && a.xmode != MVAE_X_DENSE) ||
-            (a.signal_done && !a.hs))
+            (a.wait_ready && a.chunk_steps == 1) || (a.signal_done && !a.hs))      // (one-step chunks: see mvae_rnn_fwd)
             return MVAE_E_ARG;
         if (a.H != RH || a.dtype != MVAE_BF16 || a.seq_layout != MVAE_TILE16P || (a.cell != MVAE_LSTM && a.cell != MVAE_GRU) ||
             a.cell != f.cell || a.xmode == MVAE_X_SCALAR || !a.hs || (a.acts != nullptr) != (f.acts != nullptr) ||

@@ -67,6 +67,32 @@ __device__ __forceinline__ void w8_barrier() {
     if (W8_ABL_NOBAR) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     else lds_barrier();
 }
+// lstm_bwd_w8_body publishes the chunks of a TILE16P stack, whose consumers count mvae_rnn_producer_waves(MVAE_TILE16P) = 4 increments
+// per workgroup and chunk, with 8 waves (it used to add 8: a consumer was released when half the waves had stored their da rows).
+// if (t == bound): every wave drains its write-through stores, the workgroup meets (t and bound are workgroup-uniform), and waves
+// 0..3 add 1 each - behind the stores of all eight.  One asm block with scalar control flow, as the helpers of common.h.
+__device__ __forceinline__ void w8_signal_done_4_of_8_if(int t, int bound, int wave, uint32_t* counter) {
+    unsigned t0, t1;
+    unsigned long long save;
+    asm volatile(
+        "s_cmp_lg_u32 %3, %4\n\t"
+        "s_cbranch_scc1 L_skip_%=\n\t"
+        "s_waitcnt vmcnt(0)\n\t"
+        "s_barrier\n\t"
+        "s_cmp_ge_u32 %5, 4\n\t"
+        "s_cbranch_scc1 L_skip_%=\n\t"
+        "s_mov_b64 %2, exec\n\t"
+        "s_mov_b64 exec, 1\n\t"
+        "v_mov_b32 %0, 0\n\t"
+        "v_mov_b32 %1, 1\n\t"
+        "global_atomic_add %0, %1, %6 sc1\n\t"
+        "s_mov_b64 exec, %2\n\t"
+        "s_waitcnt vmcnt(0)\n"
+        "L_skip_%=:"
+        : "=&v"(t0), "=&v"(t1), "=&s"(save)
+        : "s"(t), "s"(bound), "s"(wave), "s"(counter)
+        : "memory", "scc");
+}
 __device__ __forceinline__ float hsig(float x) { return __builtin_amdgcn_fmed3f(__builtin_fmaf(0.2f, x, 0.5f), 0.0f, 1.0f); }
 
 #include "rnn_multi.h"
@@ -280,9 +306,13 @@ __device__ __forceinline__ void gru_fwd_w8_body(const mvae_rnn_fwd_args& a, cons
         unsigned char* hcur = hbuf + PAR * 8192;
         unsigned char* hnext = hbuf + (1 - PAR) * 8192;
         pinu(hw0); pinu(tl0);
-        // pipelined stack: x of step t+2 is requested during this step - its chunk must have been published
-        if (XMODE == MVAE_X_DENSE && cs_steps && a.wait_ready && t + 2 < T && t + 2 == phi)
-            wave_wait_ge(uniform_ptr(a.wait_ready + pk + 1), wait_value, a.status);
+        // pipelined stack: x of step t+2 is requested during this step - its chunk must have been published.  pk / phi move on
+        // at the END of step t == phi (the publish below): in that step the chunk being read ahead of is already pk + 1, ending
+        // before phi + chunk_steps - with chunk_steps == 2 that is the step whose request crosses into the next chunk
+        if (XMODE == MVAE_X_DENSE && cs_steps && a.wait_ready && t + 2 < T) {
+            const int moved = t == phi ? 1 : 0;
+            if (t + 2 == phi + (moved ? cs_steps : 0)) wave_wait_ge(uniform_ptr(a.wait_ready + pk + 1 + moved), wait_value, a.status);
+        }
         pins(acts_p[0]); pins(acts_p[1]); pins(acts_p[2]); pins(hs_p); pins(hh_prev_p);
         pins(x_p[0]); pins(x_p[1]); pins(x_p[2]);
         // this step's z and candidate inputs were requested two steps ago: everything but the previous step's instructions has retired
@@ -1086,7 +1116,7 @@ __device__ __forceinline__ void lstm_bwd_w8_body(const mvae_rnn_bwd_args& a, con
         });
         asm volatile("s_nop 9" : "+v"(acc[0]), "+v"(acc[1]));
         da_p -= da_step;
-        wave_signal_done_if<false>(t, __builtin_amdgcn_readfirstlane(psig), uniform_ptr(a.signal_done + pk));
+        w8_signal_done_4_of_8_if(t, __builtin_amdgcn_readfirstlane(psig), w, uniform_ptr(a.signal_done + pk));
         {
             const bool adv = cs_steps && t == plo;
             pk -= adv ? 1 : 0;
@@ -1225,7 +1255,7 @@ int mvae_rnn_fwd_multi_w8(const mvae_rnn_fwd_args* problems, int32_t n, const mv
         const mvae_rnn_fwd_args& a = problems[i];
         if (!a.u_pack || a.T <= 0 || a.B <= 0 || (a.B % 16) || a.chunk_steps < 0 ||
             ((a.wait_ready || a.signal_done) && a.chunk_steps == 0) || (a.wait_ready && a.xmode != MVAE_X_DENSE) ||
-            (a.signal_done && !a.hs))
+            (a.wait_ready && a.chunk_steps == 1) || (a.signal_done && !a.hs))      // (one-step chunks: see mvae_rnn_fwd)
             return MVAE_E_ARG;
         if (a.H != RH || a.dtype != MVAE_BF16 || a.seq_layout != MVAE_TILE16Q || a.cell != MVAE_GRU || a.xmode == MVAE_X_SCALAR || !a.hs ||
             (a.acts != nullptr) != (f.acts != nullptr) || a.cs)

@@ -39,6 +39,8 @@ class PhaseLaunches(object):
         cs = self.pipe_chunk
         while r.T % cs:
             cs //= 2
+        if cs < 2:          # (an odd T: the forward kernels do not wait by one-step chunks, include/midivae_hip.h - one chunk then)
+            cs = r.T
         blocks = self.xpand_blocks if idx is None else self.index_dense_blocks
         sync, target, _ = self._sync_region(5 if idx is None else 9, 1, r.T // cs, self._rnn_waves(r) * blocks, 0)      # (the producer's blocks are blocks of the launch: as many waves each)
         xp = self._v(p + ".xp", r.T, B, s.GH)

@@ -220,16 +220,18 @@ def rnn_forward(cell, xp, U, h0, c0=None, rec_act="hard_sigmoid"):
     return hs, cs, acts
 
 
-def rnn_backward(cell, hs, cs, acts, U, dhs_ext=None, dh_last=None, rec_act="hard_sigmoid"):
+def rnn_backward(cell, hs, cs, acts, U, dhs_ext=None, dh_last=None, rec_act="hard_sigmoid", dc_last=None):
     """BPTT.  dhs_ext (T,B,H): gradient arriving at every h_t (t=1..T stored at index t-1) from above;
-    dh_last (B,H): extra gradient at the final state.  Returns da (T,B,G*H) (= d xp), dU, dh0, dc0."""
+    dh_last (B,H): extra gradient at the final state; dc_last (B,H): LSTM, gradient arriving at the final CELL state (a
+    sequence run as time chunks from the last to the first: dh_last, dc_last = the dh0, dc0 of the chunk behind).
+    Returns da (T,B,G*H) (= d xp), dU, dh0, dc0."""
     _dhs = _REC_ACT[rec_act][1]                  # (test-only switch, see rnn_forward)
     T, B, GH = acts.shape
     H = U.shape[0]
     da = np.zeros_like(acts)
     dU = np.zeros_like(U)
     dh = np.zeros((B, H), acts.dtype) if dh_last is None else dh_last.copy()
-    dc = np.zeros((B, H), acts.dtype)
+    dc = np.zeros((B, H), acts.dtype) if dc_last is None else dc_last.copy()
     for t in range(T - 1, -1, -1):
         d = dh + (dhs_ext[t] if dhs_ext is not None else 0.0)
         hp = hs[t]

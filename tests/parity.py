@@ -192,6 +192,151 @@ def rnn_backward_problem(cellname, H, T, B, ext, rnd):
     return U, hs_o, cs_o, acts_o, dext, dlast
 
 
+# ---- hand-over, carried state and phase launches (test_rnn_handover_gpu.py; the CPU side of it: test_parity_cpu.py) ---------
+# States as column blocks: ld = 3 H, the block at column H, every other column a finite sentinel.
+STATE_LD_FACTOR, STATE_SENTINEL, WORD_SENTINEL = 3, -777.25, 0x5A5A5A5A
+# A sequence as consecutive launches: T -> the chunk lengths.  T = 8 as 3 + 5: an odd first chunk shifts the two-step unrolling of the
+# slot-interleaved and two-waves-per-SIMD GRU kernels.
+TIME_SPLITS = {7: [(3, 4), (1, 6)], 8: [(3, 5)]}
+# (H, B, arithmetic mode) of the generic kernels' cases (T = 7); the resident families run H = 256, B = 32, bf16
+GENERIC_SHAPES = [(64, 5, F32), (128, 20, BF16)]
+RES_H, RES_B, HANDOVER_T = 256, 32, 7
+
+
+def rnn_forward_inputs(cellname, H, T, B, xmode, seed, rnd=None, K=7):
+    """test_ops_gpu.test_rnn_forward's problem as a Problem: ``rnn_problem``'s U, h0, c0 and the inputs of one input mode ("dense": xp
+    (T, B, GH); "index": idx (T, B) into table (K, GH) = W + b; "scalar": xs (T, B), w_row, bias; "const": xp0 (B, GH)), ``rnd``
+    rounding what the kernel is handed in its storage type; xp = the pre-activation inputs the oracle gets, and the oracle's hs, cs,
+    acts on them (float64, unrounded)."""
+    rnd = rnd or (lambda a: a)
+    rng, G, U, W, b, h0, c0 = rnn_problem(cellname, H, T, B, seed, K)
+    GH = G * H
+    pb = Problem(cellname=cellname, H=H, T=T, B=B, G=G, xmode=xmode, U=U, h0=h0, c0=c0 if cellname == "LSTM" else None, idx=None,
+                 table=None, xs=None, w_row=None, bias=None, xp0=None, rng=rng)
+    if xmode == "dense":
+        pb.xp = rnd(rng.standard_normal((T, B, GH)) * 0.5)
+    elif xmode == "index":
+        pb.idx, pb.table = rng.integers(0, K, (T, B)), rnd(W + b)
+        pb.xp = pb.table[pb.idx]
+    elif xmode == "scalar":
+        pb.xs, pb.w_row, pb.bias = rng.random((T, B)), W[0], b
+        pb.xp = pb.xs[..., None] * W[0] + b
+    else:
+        assert xmode == "const", xmode
+        pb.xp0 = rnd(rng.standard_normal((B, GH)) * 0.5)
+        pb.xp = np.broadcast_to(pb.xp0[None], (T, B, GH)).copy()
+    pb.hs, pb.cs, pb.acts = vo.rnn_forward(cellname, pb.xp, U, pb.h0, pb.c0)
+    return pb
+
+
+def carried_cell_gradient(H, B):
+    """a gradient arriving at the final CELL state of an LSTM (dc_last), at the scale of ``rnn_backward_problem``'s dh_last"""
+    return np.random.default_rng(1000 + H + B).standard_normal((B, H)) * 0.1
+
+
+def split_bounds(lengths):
+    """chunk lengths -> [(t0, t1)] in time order"""
+    t, out = 0, []
+    for n in lengths:
+        out.append((t, t + n))
+        t += n
+    return out
+
+
+def forward_in_chunks(cellname, xp, U, h0, c0, lengths):
+    """the oracle's forward pass as consecutive runs over time chunks, chunk k + 1 starting from the final h (and c) of chunk k; the
+    assembled hs (T + 1, B, H), cs, acts.  Slot t0 of hs / cs is written by both neighbours, the later one last."""
+    T, B, GH = xp.shape
+    H = U.shape[0]
+    hs, acts = np.full((T + 1, B, H), np.nan), np.full((T, B, GH), np.nan)
+    cs = np.full((T + 1, B, H), np.nan) if cellname == "LSTM" else None
+    h, c = h0, c0
+    for t0, t1 in split_bounds(lengths):
+        hs_k, cs_k, acts_k = vo.rnn_forward(cellname, xp[t0:t1], U, h, c)
+        hs[t0:t1 + 1], acts[t0:t1] = hs_k, acts_k
+        h = hs_k[-1]
+        if cs is not None:
+            cs[t0:t1 + 1], c = cs_k, cs_k[-1]
+    return hs, cs, acts
+
+
+def backward_in_chunks(cellname, hs, cs, acts, U, dext, dlast, lengths, dclast=None):
+    """the oracle's BPTT from the last time chunk to the first, dh_last / dc_last of a chunk = dh0 / dc0 of the chunk behind it;
+    the assembled da and the first chunk's dh0, dc0"""
+    da = np.full(acts.shape, np.nan)
+    dh, dc = dlast, dclast
+    for t0, t1 in reversed(split_bounds(lengths)):
+        da[t0:t1], _, dh, dc = vo.rnn_backward(cellname, hs[t0:t1 + 1], cs[t0:t1 + 1] if cs is not None else None, acts[t0:t1], U,
+                                               dext[t0:t1] if dext is not None else None, dh, dc_last=dc)
+    return da, dh, dc
+
+
+# Chunk counters of the time-pipelined kernels: chunk k = steps [k cs, (k + 1) cs) (the last one may be short).  Forward: hs slot
+# t + 1 belongs to step t; chunk k is published behind slot min((k + 1) cs, T), chunks in ascending order.  Backward: steps run from
+# T - 1 down; chunk k is published behind da of its FIRST step k cs, chunks in descending order.  Every producer wave adds 1:
+# mvae_rnn_producer_waves(layout) * B / 16 per chunk and launch.
+def chunk_count(T, cs):
+    return -(-T // cs)
+
+
+def chunk_of_step(t, cs):
+    return t // cs
+
+
+def chunk_steps_of(k, T, cs):
+    """(first step, one past the last step) of chunk k"""
+    return k * cs, min((k + 1) * cs, T)
+
+
+def publish_order(T, cs, forward):
+    """[(chunk, the step behind which it is published)] in the kernel's own order"""
+    n = chunk_count(T, cs)
+    if forward:
+        return [(k, chunk_steps_of(k, T, cs)[1] - 1) for k in range(n)]
+    return [(k, k * cs) for k in range(n - 1, -1, -1)]
+
+
+def expected_counters(T, cs, waves, B, launches=1):
+    """the increments of counters 0 .. chunk_count - 1 after ``launches`` launches"""
+    return [launches * waves * (B // 16)] * chunk_count(T, cs)
+
+
+COUNTER_CS = [1, 2, 3, 16]        # (1: publishing alone and the backward kernels; the forward kernels refuse it with wait_ready)
+
+
+def counter_lengths(cs):
+    """T of the chunk-counter cases of one chunk length: 1, cs - 1, cs, cs + 1, 2 cs, 2 cs + 1 (T >= 1)"""
+    return sorted({T for T in (1, cs - 1, cs, cs + 1, 2 * cs, 2 * cs + 1) if T >= 1})
+
+
+LIVE_T, LIVE_CS_FWD, LIVE_CS_BWD = [8, 9], [2, 4], [1, 2, 4]
+COUNTER_T_MAX = 33
+
+
+def handover_t_cs():
+    """every (T, chunk_steps) the GPU tests run a counter rule at"""
+    out = {(T, cs) for cs in COUNTER_CS for T in counter_lengths(cs)}
+    out |= {(T, cs) for T in LIVE_T for cs in LIVE_CS_FWD + LIVE_CS_BWD}
+    out |= {(XPAND_T, XPAND_CS)}
+    return sorted(out)
+
+
+# Phase launches: (T, B, input mode, upstream gradient?) of the problems of one launch - three row-tile counts, so every base[] differs
+PHASE_PROBLEMS = [(4, 16, "index", False), (16, 32, "const", True), (33, 48, "dense", True), (16, 16, "dense", False)]
+XPAND_T, XPAND_CS, XPAND_B, XPAND_BLOCKS = 16, 4, 32, [2, 16]
+
+
+def phase_seed(i, cellname):
+    return 300 + 10 * i + len(cellname)
+
+
+def xpand_problem(GH, R, seed, K=61):
+    """the inputs of an expansion producer: a 1-feature roll xs (R), w and bias (GH); or index rows idx (R) into a table (K, GH)"""
+    rng = np.random.default_rng(seed)
+    return Problem(xs=rng.random(R), w=rng.standard_normal(GH) * 0.4, bias=rng.standard_normal(GH) * 0.2,
+                   idx=rng.integers(0, K, R), table=rng.standard_normal((K, GH)) * 0.5)
+
+
 # ---- the saturated regime: clipped hard-sigmoid gates, tanh far out, a cell state past the range of e^{2c} ------------------
 SAT_STD, SAT_BIG = 2.0, 60.0       # spread of the pre-activation inputs; the planted rows' value (exact in bf16)
 

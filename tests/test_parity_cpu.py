@@ -487,3 +487,111 @@ def test_engine_saturated_problem_keeps_its_distance_from_the_clips(cell):
     assert len(margins) == 8
     for share, dist in margins:
         assert share >= eng_t.SATURATED_MIN_SHARE and dist >= eng_t.SATURATED_MIN_DISTANCE, margins
+
+
+# ---- hand-over, carried state and chunk counters (the CPU side of test_rnn_handover_gpu.py) ------------------------------
+def _handover_shapes():
+    """(H, B, arithmetic mode, T) of every carried-state case of the GPU tests"""
+    return [(H, B, dt, par.HANDOVER_T) for H, B, dt in par.GENERIC_SHAPES] + [(par.RES_H, par.RES_B, BF16, T) for T in sorted(par.TIME_SPLITS)]
+
+
+def _rnd(dt):
+    return bf if dt == BF16 else (lambda a: a)
+
+
+@pytest.mark.parametrize("cellname", ["GRU", "LSTM", "SimpleRNN"])
+def test_oracle_in_time_chunks_with_carried_state_equals_the_whole_sequence(cellname):
+    """the slicing and carry plumbing of the GPU tests' part 2, on their own inputs: the oracle run chunk by chunk (h0 = h_last,
+    c0 = c_last forward; dh_last = dh0, dc_last = dc0 from the last chunk to the first) equals its whole-sequence run to 1e-12"""
+    for H, B, dt, T in _handover_shapes():
+        if cellname == "SimpleRNN" and H == par.RES_H:
+            continue
+        for xmode in ("dense", "index"):
+            pb = par.rnn_forward_inputs(cellname, H, T, B, xmode, seed=H + B + T, rnd=_rnd(dt))
+            for lengths in par.TIME_SPLITS[T]:
+                assert sum(lengths) == T
+                hs, cs, acts = par.forward_in_chunks(cellname, pb.xp, pb.U, pb.h0, pb.c0, lengths)
+                np.testing.assert_allclose(hs, pb.hs, rtol=0, atol=1e-12)
+                np.testing.assert_allclose(acts, pb.acts, rtol=0, atol=1e-12)
+                if cs is not None:
+                    np.testing.assert_allclose(cs, pb.cs, rtol=0, atol=1e-12)
+        for ext in (True, False):
+            U, hs_o, cs_o, acts_o, dext, dlast = par.rnn_backward_problem(cellname, H, T, B, ext, _rnd(dt))
+            dclast = par.carried_cell_gradient(H, B) if cellname == "LSTM" else None
+            da_w, _, dh0_w, dc0_w = vo.rnn_backward(cellname, hs_o, cs_o, acts_o, U, dext, dlast, dc_last=dclast)
+            for lengths in par.TIME_SPLITS[T]:
+                da, dh0, dc0 = par.backward_in_chunks(cellname, hs_o, cs_o, acts_o, U, dext, dlast, lengths, dclast)
+                np.testing.assert_allclose(da, da_w, rtol=0, atol=1e-12)
+                np.testing.assert_allclose(dh0, dh0_w, rtol=0, atol=1e-12)
+                if cellname == "LSTM":
+                    np.testing.assert_allclose(dc0, dc0_w, rtol=0, atol=1e-12)
+
+
+def test_oracle_dc_last_defaults_to_zero_and_reaches_dc0():
+    """rnn_backward(dc_last=None) is what it was; a dc_last changes da and dc0 of an LSTM and nothing of a GRU"""
+    U, hs_o, cs_o, acts_o, dext, dlast = par.rnn_backward_problem("LSTM", 64, 7, 5, True, lambda a: a)
+    base = vo.rnn_backward("LSTM", hs_o, cs_o, acts_o, U, dext, dlast)
+    zero = vo.rnn_backward("LSTM", hs_o, cs_o, acts_o, U, dext, dlast, dc_last=np.zeros((5, 64)))
+    for a, b in zip(base, zero):
+        np.testing.assert_array_equal(a, b)
+    dcl = par.carried_cell_gradient(64, 5)
+    with_dc = vo.rnn_backward("LSTM", hs_o, cs_o, acts_o, U, dext, dlast, dc_last=dcl)
+    twice = vo.rnn_backward("LSTM", hs_o, cs_o, acts_o, U, dext, dlast, dc_last=2.0 * dcl)
+    for k in (0, 2, 3):                                           # BPTT is linear in the gradients that arrive: da, dh0, dc0
+        np.testing.assert_allclose(twice[k] - with_dc[k], with_dc[k] - base[k], rtol=0, atol=1e-12)
+        assert np.abs(with_dc[k] - base[k]).max() > 1e-4
+    Ug, hs_g, _, acts_g, dext_g, dlast_g = par.rnn_backward_problem("GRU", 64, 7, 5, True, lambda a: a)
+    for a, b in zip(vo.rnn_backward("GRU", hs_g, None, acts_g, Ug, dext_g, dlast_g)[:3],
+                    vo.rnn_backward("GRU", hs_g, None, acts_g, Ug, dext_g, dlast_g, dc_last=dcl)[:3]):        # (da, dU, dh0)
+        np.testing.assert_array_equal(a, b)
+
+
+def _walk_forward(T, cs):
+    """a step-by-step walk that MIRRORS the forward kernels' own bookkeeping (pk / phi, advanced at a chunk's first step) - it pins
+    the closed forms of tests/parity.py to the code's logic, it is not a second derivation; the independent checks are the ones
+    beside it (floor(t / cs) per step, the chunks' step ranges covering range(T) once).  Returns (chunk of every step, [(chunk,
+    step behind which it is published)])"""
+    pk, phi, of, pub = 0, cs, [], []
+    for t in range(T):
+        if t == phi:            # the first step of the next chunk: the previous chunk's last hs slot is written during it
+            pub.append((pk, t - 1))
+            pk, phi = pk + 1, phi + cs
+        of.append(pk)
+    pub.append((pk, T - 1))
+    return of, pub
+
+
+def _walk_backward(T, cs):
+    """the same for the backward kernels (pk / plo, from the last step down): a mirror of their bookkeeping"""
+    pk = (T - 1) // cs
+    plo, of, pub = pk * cs, {}, []
+    for t in range(T - 1, -1, -1):
+        of[t] = pk
+        if t == plo:
+            pub.append((pk, t))
+            pk, plo = pk - 1, plo - cs
+    return [of[t] for t in range(T)], pub
+
+
+def test_chunk_counter_rule_against_a_walk_over_the_steps():
+    """parity.chunk_count / chunk_of_step / chunk_steps_of / publish_order at every (T, chunk_steps) the GPU tests use"""
+    cases = par.handover_t_cs()
+    assert (8, 2) in cases and (33, 16) in cases and (1, 16) in cases and (9, 1) in cases
+    for T, cs in cases:
+        for forward, walk in ((True, _walk_forward), (False, _walk_backward)):
+            of, pub = walk(T, cs)
+            assert of == [par.chunk_of_step(t, cs) for t in range(T)] == [int(np.floor(t / cs)) for t in range(T)], (T, cs)
+            assert pub == par.publish_order(T, cs, forward), (T, cs, forward)
+            assert len(pub) == par.chunk_count(T, cs) == max(of) + 1
+        steps = [t for k in range(par.chunk_count(T, cs)) for t in range(*par.chunk_steps_of(k, T, cs))]
+        assert steps == list(range(T)), (T, cs)
+        assert par.expected_counters(T, cs, 8, 48, launches=2) == [48] * par.chunk_count(T, cs)
+    for cs in par.COUNTER_CS:
+        assert all(1 <= T <= par.COUNTER_T_MAX for T in par.counter_lengths(cs))
+
+
+def test_phase_launch_problems_stay_small():
+    """the resident kernels wait for each other inside one launch: the GPU tests' phase launches stay under 24 workgroups"""
+    assert sum(B // 16 for _, B, _, _ in par.PHASE_PROBLEMS) < 24
+    assert max(par.XPAND_BLOCKS) + par.XPAND_B // 16 < 24 and par.XPAND_T % par.XPAND_CS == 0
+    assert sorted({B for _, B, _, _ in par.PHASE_PROBLEMS}) == [16, 32, 48] and {T for T, _, _, _ in par.PHASE_PROBLEMS} == {4, 16, 33}
