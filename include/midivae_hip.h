@@ -307,7 +307,11 @@ typedef struct {
     float grad_scale;             /* multiplies d(logits) (loss weight of the head)                          */
     float* probs;                 /* (R,N) f32 or NULL                                                       */
     uint8_t* argmax;              /* (R) or NULL: first-max index (kind 0), round(p) (kind 1)                */
-    void* dlogits;                /* (R,NP) dtype, NP = mvae_head_np(N); required if want_grad; columns [N,NP) = 0 */
+    void* dlogits;                /* (R,NP) dtype, NP = mvae_head_np(N); required if want_grad.  kind 0 (softmax) writes every
+                                     column: [0,N) the gradient, [N,NP) zeros.  kind 1 (sigmoid) stores column 0 ONLY and
+                                     leaves columns [1,NP) to the caller, who must have zeroed them once before anything
+                                     reads the pad (the dW GEMM, the fused dhs' wc pad): engine_buffers.py allocates the
+                                     buffer with torch.zeros and nothing else writes there                            */
     float* scalars;               /* (2) accumulated atomically                                              */
     int32_t b_stride, b_valid;    /* rows are (t, b) with b = row % b_stride; rows with b >= b_valid are padding and
                                      are excluded from the metric count (0,0 = every row counts)             */
