@@ -16,6 +16,11 @@
  *   - every pointer is a DEVICE pointer owned by the caller; nothing here allocates, frees or synchronises;
  *   - `stream` is a hipStream_t passed as void*; all work is enqueued on it, in order;
  *   - return value: 0 = enqueued, negative = rejected (MVAE_E_*), nothing enqueued; never throws;
+ *     every limit below is checked BEFORE the first thing an entry point enqueues (a fill of its output and the first of
+ *     several launches included): MVAE_E_ARG for a NULL required pointer, an extent <= 0, an enum value outside its range, a
+ *     leading dimension below the row it strides over, a stated divisibility or alignment; MVAE_E_UNSUPPORTED for a well-formed
+ *     problem no kernel is built for.  tests/abi_contract.py holds these limits as a table, one row each.  An element count
+ *     (size_t n; rows / cols of mvae_copy2d_f32; n of mvae_scalars_accumulate) may be 0: MVAE_OK, nothing to do;
  *   - sequences are TIME-MAJOR: element (t, b, c) of a (T, B, C) array lives at (t*B + b)*C + c;
  *   - `dtype` selects the MFMA operand type AND the storage type of sequence activations:
  *         MVAE_F32  : f32 operands (v_mfma_f32_16x16x4_f32), f32 storage  -- parity mode
@@ -101,8 +106,8 @@ typedef struct {
     float* h_last;         /* (B,H) or NULL                                                                   */
     float* c_last;         /* LSTM: final cell state (B,H) f32 or NULL (row stride h_last_ld): lets a sequence be
                               run as consecutive launches (time chunks) without rounding the carried state     */
-    int32_t h0_ld;         /* row stride of h0 / c0 in floats (0 = H): states may be column blocks of a wider buffer */
-    int32_t h_last_ld;     /* row stride of h_last (0 = H)                                                     */
+    int32_t h0_ld;         /* row stride of h0 / c0 in floats (0 = H, else >= H): states may be column blocks of a wider buffer */
+    int32_t h_last_ld;     /* row stride of h_last / c_last (0 = H, else >= H)                                 */
     /* ---- time-pipelined stacks (slot-interleaved LSTM kernels only; all NULL / 0 otherwise) ----------------------
      * A stack of layers runs as ONE launch per layer, plus ONE persistent mvae_gemm launch per layer interface (its
      * chunk_* fields): layer l publishes chunk k (chunk_steps time steps) of hs in a counter, the GEMM waits for it,
@@ -111,17 +116,21 @@ typedef struct {
      * words in device memory, zeroed by the caller before the launches.  Every producer stores the data it hands over
      * WRITE-THROUGH (sc1) and publishes behind a drained vmcnt - no L2 write-back: a buffer_wbl2 per hand-over writes back
      * the whole XCD's L2 and stalls the recurrent workgroups that share it (7.5 % of a training step). */
-    int32_t chunk_steps;         /* time steps per pipeline chunk; chunk k = steps [k*chunk_steps, (k+1)*chunk_steps).
+    int32_t chunk_steps;         /* time steps per pipeline chunk; chunk k = steps [k*chunk_steps, (k+1)*chunk_steps); >= 1 with
+                                    wait_ready or signal_done (0 or negative: MVAE_E_ARG; on any other seq_layout than
+                                    MVAE_TILE16P / MVAE_TILE16Q the hand-over fields are MVAE_E_UNSUPPORTED).
                                     With wait_ready it must be >= 2 (1: MVAE_E_ARG, also from mvae_rnn_fwd_multi): the forward
                                     kernels read xp one or two steps ahead and wait once per chunk.  Publishing alone
                                     (signal_done) and the backward kernels (mvae_rnn_bwd_args) take 1                      */
-    const uint32_t* wait_ready;  /* [chunks] chunk k of xp may be read once wait_ready[k] >= wait_value (kernel polls)    */
+    const uint32_t* wait_ready;  /* [chunks] chunk k of xp may be read once wait_ready[k] >= wait_value (kernel polls);
+                                    MVAE_X_DENSE only (MVAE_E_ARG with any other xmode)                                    */
     uint32_t wait_value;         /* 0 = 1                                                                                 */
     uint32_t* signal_done;       /* [chunks] += mvae_rnn_producer_waves(seq_layout) * B/16 in all (1 per publishing wave) once
                                     chunk k of hs is complete and visible; needs hs (MVAE_E_ARG without)                   */
     uint32_t* status;            /* [1] set non-zero if a wait timed out (~2-4 s): results are invalid                    */
     int32_t seq_layout;    /* layout of xp, acts and cs (hs is always row-major): MVAE_ROWMAJOR, MVAE_TILE16 or
-                              MVAE_TILE16P.  The tiled layouts need B % 16 == 0 and select the resident-weights kernels
+                              MVAE_TILE16P.  The tiled layouts need B % 16 == 0 (else MVAE_E_UNSUPPORTED; MVAE_E_ARG from the
+                              phase launches) and select the resident-weights kernels
                               (H=256, bf16): TILE16 the phased ones, TILE16P the slot-interleaved ones (LSTM, GRU; not
                               for MVAE_X_SCALAR inputs)                                                            */
     int32_t table_layout;  /* MVAE_X_INDEX: MVAE_TABLE_ROWMAJOR (0), or MVAE_TABLE_PAIRED (1: MVAE_PREP_MAKE_TABLE with c = 1) -
@@ -148,8 +157,8 @@ typedef struct {
     void* rh;              /* GRU: (T,B,H) dtype r_t*h_{t-1} (left operand of the candidate-kernel gradient)  */
     float* dh0;            /* (B,H) or NULL                                                                   */
     float* dc0;            /* LSTM: (B,H) or NULL                                                             */
-    int32_t dh_last_ld;    /* row stride of dh_last (0 = H)                                                   */
-    int32_t dh0_ld;        /* row stride of dh0 / dc0 (0 = H)                                                 */
+    int32_t dh_last_ld;    /* row stride of dh_last / dc_last (0 = H, else >= H)                              */
+    int32_t dh0_ld;        /* row stride of dh0 / dc0 (0 = H, else >= H)                                      */
     /* time-pipelined stacks, as in mvae_rnn_fwd_args: wait_ready gates dhs_ext (chunk k = steps [k*cs, (k+1)*cs), consumed
      * from the last chunk to the first), signal_done publishes da (and rh): chunk k += mvae_rnn_producer_waves(seq_layout) * B/16 in
      * all once da of its steps is complete and visible.  chunk_steps may be 1 here */
@@ -162,7 +171,7 @@ typedef struct {
 } mvae_rnn_bwd_args;
 int mvae_rnn_bwd(const mvae_rnn_bwd_args* a, void* stream);
 
-/* Pack a recurrent kernel U (H, G*H) f32 row-major into MFMA A-fragment order.
+/* Pack a recurrent kernel U (H, G*H) f32 row-major into MFMA A-fragment order; H a positive multiple of 64.
  * direction 0: forward  (rows of A = gate columns, contraction over h)      -> G*H*H elements
  * direction 1: backward (rows of A = hidden units, contraction over gate columns) -> G*H*H elements */
 int mvae_pack_recurrent(const float* U, void* out, int32_t cell, int32_t H, int32_t dtype, int32_t direction,
@@ -170,9 +179,10 @@ int mvae_pack_recurrent(const float* U, void* out, int32_t cell, int32_t H, int3
 
 /* ---------------------------------------------------------------------------------------------------------
  * GEMM  C = alpha * opA(A) * opB(B) [+ bias] [-> tanh]   (Dense layers :484,487,506-507,563-567; input
- * projections of stacked layers; all parameter gradients).  Row-major with leading dimensions.
+ * projections of stacked layers; all parameter gradients).  Row-major with leading dimensions, each at least the length of
+ * the row it strides over (lda >= K, or M with trans_a; ldb >= N, or K with trans_b; ldc >= N for a row-major C): MVAE_E_ARG below.
  *   a_kind: MVAE_F32 / MVAE_BF16, or MVAE_A_ONEHOT: A is never stored - opA(A)[m,k] = (idx[k] == m)
- *           (requires trans_a = 1), used for the gradient of an X_INDEX table.  idx holds one byte per k; the fast
+ *           (requires trans_a = 1; lda is not read), used for the gradient of an X_INDEX table.  idx holds one byte per k; the fast
  *           kernel takes M <= 256 (two 128-row tiles; rows >= M are computed and never stored).
  *   Fast-kernel shapes (bf16 B, bf16 or one-hot A, K % 64 == 0): N a multiple of 128 - or, for an accumulating row-major
  *           C += A^T B with row-contiguous B and no bias, ANY N: full 128-column tiles plus one narrow last tile
@@ -198,8 +208,8 @@ typedef struct {
                                      recurrent launches (which need whole idle CUs) run beside it                 */
     int32_t sys_release;          /* != 0: every workgroup ends with a system-scope release (L2 write-back), so that a
                                      kernel ALREADY RUNNING on another XCD sees C after a stream-ordered flag write  */
-    /* persistent chunked mode (fast bf16 path only, split_k <= 1, max_blocks > 0 = the persistent grid): the M rows are
-     * processed in chunks of chunk_rows (multiple of 128); chunk c starts once chunk_wait[c] >= chunk_wait_value and is
+    /* persistent chunked mode (fast bf16 path only, split_k <= 1, no accumulate, 1 <= max_blocks <= 256 = the persistent grid):
+     * the M rows are processed in chunks of chunk_rows (multiple of 128 that divides M); chunk c starts once chunk_wait[c] >= chunk_wait_value and is
      * published by chunk_done[c] += 1 per wave (4 * max_blocks in total).  chunk_reverse: last chunk first. */
     int32_t chunk_rows, chunk_reverse;
     const uint32_t* chunk_wait;
@@ -215,7 +225,8 @@ typedef struct {
      * partitions: workgroup (tile, p) takes rows [c*k_chunk_rows + p*k_chunk_rows/P, ... + k_chunk_rows/P) of every chunk,
      * keeps its 128 x 128 accumulator in registers across ALL chunks and adds it to C once at the end - one workgroup per
      * (tile, partition), all resident for the whole launch (max_blocks must be 0).  k_reverse: last chunk first (BPTT order).
-     * What is left when the producer ends is one chunk's share, not the whole GEMM.  chunk_status reports a timed-out wait. */
+     * What is left when the producer ends is one chunk's share, not the whole GEMM.  chunk_status reports a timed-out wait.
+     * MVAE_E_ARG unless k_chunk_rows divides K, k_chunk_rows / split_k is a multiple of 64 and the launch has at most 256 workgroups. */
     const uint32_t* k_wait;
     uint32_t k_wait_value;
     int32_t k_chunk_rows, k_reverse;
@@ -290,7 +301,10 @@ int mvae_rnn_bwd_multi(const mvae_rnn_bwd_args* problems, int32_t n, void* strea
  * (t, b) rows at once.  Replaces Dense(softmax)+categorical_crossentropy (:542,:593 with :338,:367),
  * Dense(sigmoid)+mse (:631,:374) and the per-output 'accuracy' metric (:339).
  *   kind 0: softmax + categorical cross-entropy (targets as class index per row, or -1 = all-zero target)
- *   kind 1: sigmoid + squared error (targets f32 per row), N must be 1
+ *   kind 1: sigmoid + squared error (targets f32 per row), N must be 1      (any other kind: MVAE_E_ARG)
+ * H a multiple of 16 (f32) / 32 (bf16), else MVAE_E_UNSUPPORTED.
+ * Decode launches pass no target: target_idx / target_val, row_weight and scalars may each be NULL - no loss term, weight 1,
+ * nothing accumulated - and the launch still writes probs / argmax (engine.py's predict path relies on it).
  * Row weights: rw[row] multiplies the row's score (already divided by the Keras normalisers on the host).
  * scalars[0] += sum rw*score, scalars[1] += number of rows whose argmax (or rounding) matches the target.
  * --------------------------------------------------------------------------------------------------------- */
@@ -301,8 +315,8 @@ typedef struct {
     const void* hs;               /* (R,H) dtype                                                             */
     const void* wt;               /* (NP,H) dtype: W^T zero-padded to NP rows (mvae_transpose_convert)       */
     const float* bias;            /* (N)                                                                     */
-    const uint8_t* target_idx;    /* kind 0: (R) class index, 255 = all-zero target row                      */
-    const float* target_val;      /* kind 1: (R)                                                             */
+    const uint8_t* target_idx;    /* kind 0: (R) class index, 255 = all-zero target row, or NULL (no target) */
+    const float* target_val;      /* kind 1: (R), or NULL (no target)                                        */
     const float* row_weight;      /* (R) or NULL = 1                                                         */
     float grad_scale;             /* multiplies d(logits) (loss weight of the head)                          */
     float* probs;                 /* (R,N) f32 or NULL                                                       */
@@ -312,7 +326,7 @@ typedef struct {
                                      leaves columns [1,NP) to the caller, who must have zeroed them once before anything
                                      reads the pad (the dW GEMM, the fused dhs' wc pad): engine_buffers.py allocates the
                                      buffer with torch.zeros and nothing else writes there                            */
-    float* scalars;               /* (2) accumulated atomically                                              */
+    float* scalars;               /* (2) accumulated atomically, or NULL                                     */
     int32_t b_stride, b_valid;    /* rows are (t, b) with b = row % b_stride; rows with b >= b_valid are padding and
                                      are excluded from the metric count (0,0 = every row counts)             */
     const void* wc;               /* (H,NP) dtype: W zero-padded to NP columns (MVAE_PREP_CONVERT_PAD), or NULL */
@@ -381,7 +395,8 @@ typedef struct {
     float* z;                     /* (B,Z) out                                                               */
     float* style_probs;           /* (B,C) out or NULL                                                       */
     float* scalars;               /* (3): += inv_batch*sum_b kl_b, += sum_b rw*style CE, += style argmax hits */
-    int32_t ldz;                  /* row stride of z (0 = Z): z may be the left block of [z | history]       */
+    int32_t ldz;                  /* row stride of z (0 = Z, else >= Z): z may be the left block of [z | history].
+                                     With style_target: 1 <= C <= 64 and C <= Z (MVAE_E_ARG)                  */
 } mvae_latent_fwd_args;
 int mvae_latent_fwd(const mvae_latent_fwd_args* a, void* stream);
 
@@ -397,7 +412,7 @@ typedef struct {
     const float* style_row_weight;
     float* dmu;                   /* (B,Z)                                                                   */
     float* dlogvar;               /* (B,Z)                                                                   */
-    int32_t lddz;                 /* row stride of dz (0 = Z)                                                */
+    int32_t lddz;                 /* row stride of dz (0 = Z, else >= Z)                                     */
 } mvae_latent_bwd_args;
 int mvae_latent_bwd(const mvae_latent_bwd_args* a, void* stream);
 
@@ -406,7 +421,9 @@ int mvae_latent_bwd(const mvae_latent_bwd_args* a, void* stream);
  * Dense (tanh, when w_extra) -> z_mean / z_log_var (on the two halves of the vector when split) -> mvae_latent_fwd ->
  * S = tanh([z | history] w_init + b_init).  Same results as the separate mvae_gemm / mvae_latent_* calls, in f32 FMAs.
  * All matrices f32 row-major: w_pack (ncat*H, H), w_extra (H, H), w_mu / w_lv (H/2 or H, Z), w_init (zin, n_init).
- * B % 4 == 0 (rows >= B_valid are padding: computed, excluded from scalars and gradients); H % 8, Z % 4, zin % 4 == 0. */
+ * B % 4 == 0 (rows >= B_valid are padding: computed, excluded from scalars and gradients); H % 8, Z % 4, zin % 4 == 0,
+ * zin >= Z, n_init % 4 == 0; without the pack Dense ncat must be 1; style_target as in mvae_latent_fwd_args (MVAE_E_ARG each).
+ * MVAE_E_UNSUPPORTED: the rows of one workgroup need more than 160 KiB of LDS (run the separate calls). */
 typedef struct {
     int32_t B, B_valid, H, Z, C, ncat, zin, n_init /* columns of S */, split;
     float beta, prior_mean, prior_std, inv_batch;
@@ -442,7 +459,11 @@ typedef struct {
 int mvae_latent_chain_bwd(const mvae_latent_chain_bwd_args* a, void* stream);
 
 /* Every derived copy of the parameters a step needs, in ONE launch (25 tiny dependent kernels cost 0.3 - 0.8 ms of queue
- * latency per training step otherwise).  Each job is one of the single calls above:
+ * latency per training step otherwise).  Each job is one of the single calls above and has its limits; ALL jobs are checked
+ * before the first launch (64 jobs per launch), so a refused call (MVAE_E_ARG) has enqueued none of them.  The jobs of a launch
+ * run side by side: no two jobs of a call may write the same destination (nor the same MVAE_PREP_ADD_I32 counter).  a, b > 0 for every
+ * op but MVAE_PREP_ADD_I32; PACK_RECURRENT takes a, b multiples of 16 (finer than mvae_pack_recurrent's H % 64: the job form
+ * has no per-cell shape) with the contraction length (a forward, b backward) a multiple of 4 (f32) / 32 (bf16), c = 0 or 1:
  *   MVAE_PREP_PACK_RECURRENT   src = U (a=H, b=G*H) f32, c = direction        -> dst as mvae_pack_recurrent(kind)
  *   MVAE_PREP_MAKE_TABLE       src = W (a=K, b=N), src2 = bias (N), c = layout -> dst (K, N) kind    (mvae_make_table; c = 1:
  *                              MVAE_TABLE_PAIRED, c = 2: MVAE_TABLE_PAIRED8, see mvae_rnn_fwd_args.table_layout)

@@ -138,6 +138,29 @@ __device__ __forceinline__ void lds_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
+// ---- host: the limits include/midivae_hip.h states for EVERY recurrent problem, single launch or phase launch.  Checked before
+// anything family-specific, so that a refused call is refused whichever kernel family its shape would have selected.
+static inline bool mvae_ld_ok(int32_t ld, int32_t row) { return ld == 0 || ld >= row; }       // (0 = the row length)
+static inline int mvae_check_rnn_fwd(const mvae_rnn_fwd_args& a) {
+    if (!a.u_pack || a.T <= 0 || a.B <= 0 || a.H <= 0) return MVAE_E_ARG;
+    if (a.cell < MVAE_GRU || a.cell > MVAE_RNN || (a.dtype != MVAE_F32 && a.dtype != MVAE_BF16) || a.xmode < MVAE_X_DENSE ||
+        a.xmode > MVAE_X_CONST || a.seq_layout < MVAE_ROWMAJOR || a.seq_layout > MVAE_TILE16Q ||
+        a.table_layout < MVAE_TABLE_ROWMAJOR || a.table_layout > MVAE_TABLE_PAIRED8)
+        return MVAE_E_ARG;
+    if (!mvae_ld_ok(a.h0_ld, a.H) || !mvae_ld_ok(a.h_last_ld, a.H)) return MVAE_E_ARG;
+    if (a.chunk_steps < 0 || ((a.wait_ready || a.signal_done) && a.chunk_steps == 0)) return MVAE_E_ARG;
+    return MVAE_OK;
+}
+static inline int mvae_check_rnn_bwd(const mvae_rnn_bwd_args& a) {
+    if (!a.ut_pack || !a.hs || !a.acts || !a.da || a.T <= 0 || a.B <= 0 || a.H <= 0) return MVAE_E_ARG;
+    if (a.cell < MVAE_GRU || a.cell > MVAE_RNN || (a.dtype != MVAE_F32 && a.dtype != MVAE_BF16) || a.seq_layout < MVAE_ROWMAJOR ||
+        a.seq_layout > MVAE_TILE16Q)
+        return MVAE_E_ARG;
+    if (!mvae_ld_ok(a.dh_last_ld, a.H) || !mvae_ld_ok(a.dh0_ld, a.H)) return MVAE_E_ARG;
+    if (a.chunk_steps < 0 || ((a.wait_ready || a.signal_done) && a.chunk_steps == 0)) return MVAE_E_ARG;
+    return MVAE_OK;
+}
+
 #define MVAE_CHECK_LAUNCH()                                   \
     do {                                                      \
         hipError_t e__ = hipGetLastError();                   \

@@ -908,6 +908,23 @@ int by_trans(const mvae_gemm_args& a, hipStream_t s) {
 }
 
 
+// what the header states for every problem, whichever kernel it would run on: pointers, extents, the enum fields and the
+// leading dimensions.  Nothing is enqueued before this has passed (mvae_gemm's own fill of C included).
+int args_check(const mvae_gemm_args* a) {
+    if (!a->A || !a->B || !a->C || a->M <= 0 || a->N <= 0 || a->K <= 0) return MVAE_E_ARG;
+    if (a->a_kind < MVAE_F32 || a->a_kind > MVAE_A_ONEHOT || (a->b_kind != MVAE_F32 && a->b_kind != MVAE_BF16) ||
+        (a->c_kind != MVAE_F32 && a->c_kind != MVAE_BF16) || (a->c_layout != MVAE_ROWMAJOR && a->c_layout != MVAE_TILE16) ||
+        (a->act != MVAE_ACT_NONE && a->act != MVAE_ACT_TANH))
+        return MVAE_E_ARG;
+    if (a->a_kind == MVAE_A_ONEHOT) {
+        if (!a->trans_a) return MVAE_E_ARG;                    // (A is never stored: lda is not read)
+    } else if (a->lda < (a->trans_a ? a->M : a->K)) return MVAE_E_ARG;
+    if (a->ldb < (a->trans_b ? a->K : a->N)) return MVAE_E_ARG;
+    if (a->c_layout == MVAE_ROWMAJOR && a->ldc < a->N) return MVAE_E_ARG;
+    if (a->split_k < 0 || a->max_blocks < 0) return MVAE_E_ARG;
+    return MVAE_OK;
+}
+
 // the argument checks of a K-streaming problem (shared by mvae_gemm and mvae_gemm_kstream_multi); workgroups it needs in *wgs
 int kstream_check(const mvae_gemm_args* a, long long* wgs) {
     const int sk = a->split_k > 1 ? a->split_k : 1;
@@ -931,8 +948,7 @@ extern "C" int mvae_gemm_kstream_multi(const mvae_gemm_args* problems, int32_t n
     long long total = 0;
     for (int i = 0; i < n; ++i) {
         const mvae_gemm_args* a = problems + i;
-        if (!a->A || !a->B || !a->C || a->M <= 0 || a->N <= 0 || a->K <= 0 || a->trans_b || a->bias || a->act != MVAE_ACT_NONE)
-            return MVAE_E_ARG;
+        if (args_check(a) != MVAE_OK || a->trans_b || a->bias || a->act != MVAE_ACT_NONE) return MVAE_E_ARG;
         long long wgs = 0;
         const int rc = kstream_check(a, &wgs);
         if (rc != MVAE_OK) return rc;
@@ -960,7 +976,7 @@ extern "C" int mvae_gemm_multi(const mvae_gemm_args* problems, int32_t n, void* 
     long long total = 0;
     for (int i = 0; i < n; ++i) {
         const mvae_gemm_args* a = problems + i;
-        if (!a->A || !a->B || !a->C || a->M <= 0 || a->N <= 0 || a->K <= 0 || a->bias || a->act != MVAE_ACT_NONE) return MVAE_E_ARG;
+        if (args_check(a) != MVAE_OK || a->bias || a->act != MVAE_ACT_NONE) return MVAE_E_ARG;
         if (!a->trans_a || a->trans_b || !a->accumulate || a->c_kind != MVAE_F32 || a->c_layout != MVAE_ROWMAJOR || a->k_wait ||
             a->chunk_rows || a->chunk_wait || a->chunk_done || a->max_blocks != 0 || a->sys_release)
             return MVAE_E_UNSUPPORTED;
@@ -1006,7 +1022,7 @@ extern "C" int mvae_occupancy(int32_t which) {
 }
 
 extern "C" int mvae_gemm(const mvae_gemm_args* a, void* stream) {
-    if (!a || !a->A || !a->B || !a->C || a->M <= 0 || a->N <= 0 || a->K <= 0) return MVAE_E_ARG;
+    if (!a || args_check(a) != MVAE_OK) return MVAE_E_ARG;
     if (a->accumulate && a->c_kind != MVAE_F32) return MVAE_E_ARG;
     if (a->split_k > 1 && !a->accumulate) return MVAE_E_ARG;
     if (a->accumulate && a->act != MVAE_ACT_NONE) return MVAE_E_ARG;

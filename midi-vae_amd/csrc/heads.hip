@@ -286,6 +286,7 @@ extern "C" int mvae_head_np(int32_t N) {
 
 extern "C" int mvae_head(const mvae_head_args* a, void* stream) {
     if (!a || !a->hs || !a->wt || !a->bias || a->R <= 0 || a->N <= 0 || a->H <= 0) return MVAE_E_ARG;
+    if (a->kind != 0 && a->kind != 1) return MVAE_E_ARG;
     if (a->want_grad && !a->dlogits) return MVAE_E_ARG;
     if (a->dhs && (!a->wc || !a->want_grad || (a->R % 16) || (a->H % 16))) return MVAE_E_ARG;
     if (a->dhs && a->H > 256) return MVAE_E_UNSUPPORTED;

@@ -272,6 +272,7 @@ extern "C" int mvae_latent_chain_fwd(const mvae_latent_chain_fwd_args* a, void* 
     if ((a->w_pack && !a->pack) || (a->w_extra && !a->extra) || (a->w_init && (!a->S || a->n_init <= 0))) return MVAE_E_ARG;
     if (!a->w_pack && a->ncat != 1) return MVAE_E_ARG;
     if (a->w_init && (a->n_init % 4)) return MVAE_E_ARG;
+    if (a->style_target && (a->C <= 0 || a->C > 64 || a->C > a->Z)) return MVAE_E_ARG;      // (as mvae_latent_fwd)
     const size_t lds = fwd_lds(*a);
     if (lds > 160 * 1024) return MVAE_E_UNSUPPORTED;
     // (lds varies with the problem: the launch helper requests more than 64 KiB once per size that exceeds the last one granted)

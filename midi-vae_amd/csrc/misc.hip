@@ -402,6 +402,7 @@ extern "C" const char* mvae_build_info(void) { return "libmidivae_hip gfx950 (CD
 
 extern "C" int mvae_latent_fwd(const mvae_latent_fwd_args* a, void* stream) {
     if (!a || !a->mu || !a->logvar || !a->eps || !a->z || !a->scalars || a->B <= 0 || a->Z <= 0) return MVAE_E_ARG;
+    if (a->ldz != 0 && a->ldz < a->Z) return MVAE_E_ARG;       // (0 = Z)
     if (a->style_target && (a->C <= 0 || a->C > 64 || a->C > a->Z)) return MVAE_E_ARG;
     hipLaunchKernelGGL(latent_fwd_k, dim3((a->B + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *a);
     MVAE_CHECK_LAUNCH();
@@ -410,6 +411,7 @@ extern "C" int mvae_latent_fwd(const mvae_latent_fwd_args* a, void* stream) {
 extern "C" int mvae_latent_bwd(const mvae_latent_bwd_args* a, void* stream) {
     if (!a || !a->mu || !a->logvar || !a->eps || !a->dz || !a->dmu || !a->dlogvar || a->B <= 0 || a->Z <= 0)
         return MVAE_E_ARG;
+    if (a->lddz != 0 && a->lddz < a->Z) return MVAE_E_ARG;     // (0 = Z)
     hipLaunchKernelGGL(latent_bwd_k, dim3(nblocks((size_t)a->B * a->Z)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), *a);
     MVAE_CHECK_LAUNCH();
@@ -453,8 +455,9 @@ extern "C" int mvae_colsum_weighted(const void* X, int32_t kind, const float* wg
     return colsum_impl(X, kind, wgt, R, N, ldx, out, reinterpret_cast<hipStream_t>(stream));
 }
 extern "C" int mvae_sum_over_time(const void* X, int32_t kind, int32_t T, int32_t BN, float* out, int32_t accumulate, void* stream) {
-    if (!X || !out || T <= 0 || BN <= 0) return MVAE_E_ARG;
+    if (!X || !out || T <= 0 || BN <= 0 || (kind != MVAE_F32 && kind != MVAE_BF16)) return MVAE_E_ARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // (every refusal is above: the fill below is the first thing enqueued)
     if (!accumulate && hipMemsetAsync(out, 0, (size_t)BN * sizeof(float), s) != hipSuccess) return MVAE_E_LAUNCH;
     // split the time range so that >= ~1024 blocks exist; every block adds its partial sums atomically
     const bool vec = kind == MVAE_BF16 && (BN % 8) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
@@ -640,8 +643,30 @@ __global__ __launch_bounds__(256) void prepare_batch_k(const prep_batch pb) {
         }
     }
 }
+// the limits of one job: those of the single call it stands for (include/midivae_hip.h)
+static bool prep_job_ok(const mvae_prep_job& job) {
+    if (job.op < 0 || job.op > MVAE_PREP_BROADCAST_ROWS || !job.dst || (job.kind != MVAE_F32 && job.kind != MVAE_BF16)) return false;
+    if (job.op == MVAE_PREP_ADD_I32) return !(job.src2 && !job.src);       // (a: any increment; b, c unused)
+    if (!job.src && job.op != MVAE_PREP_ZERO) return false;
+    if (job.a <= 0 || job.b <= 0) return false;       // (the extents of dst: a negative one is a huge size_t product)
+    switch (job.op) {
+        case MVAE_PREP_PACK_RECURRENT: {
+            const int K = job.c == 0 ? job.a : job.b, KG = job.kind == MVAE_BF16 ? 32 : 4;     // as mvae_pack_recurrent
+            return job.c >= 0 && job.c <= 1 && !(job.a % 16) && !(job.b % 16) && !(K % KG);
+        }
+        case MVAE_PREP_MAKE_TABLE:
+            return job.src2 && job.c >= 0 && job.c <= 2 && !(job.c == 1 && (job.b % 32)) && !(job.c == 2 && (job.b % 256));
+        case MVAE_PREP_TRANSPOSE_CONVERT:
+        case MVAE_PREP_CONVERT_PAD: return job.c >= job.b;       // (N_pad >= N; padded row length >= b)
+        case MVAE_PREP_ZERO: return !(job.kind == MVAE_BF16 && (((size_t)job.a * job.b) & 1));
+    }
+    return true;
+}
 extern "C" int mvae_prepare_batch(const mvae_prep_job* jobs, int32_t n_jobs, void* stream) {
     if (!jobs || n_jobs < 0) return MVAE_E_ARG;
+    // every job is checked before the first launch: a refused call enqueues nothing, wherever its bad job stands
+    for (int j = 0; j < n_jobs; ++j)
+        if (!prep_job_ok(jobs[j])) return MVAE_E_ARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     for (int j0 = 0; j0 < n_jobs; j0 += PREP_MAX_JOBS) {
         prep_batch pb;
@@ -649,18 +674,6 @@ extern "C" int mvae_prepare_batch(const mvae_prep_job* jobs, int32_t n_jobs, voi
         int total = 0;
         for (int j = 0; j < pb.n; ++j) {
             const mvae_prep_job& job = jobs[j0 + j];
-            if ((!job.src && job.op != MVAE_PREP_ZERO && job.op != MVAE_PREP_ADD_I32) || !job.dst || job.op < 0 ||
-                (job.op == MVAE_PREP_ADD_I32 && job.src2 && !job.src) ||
-                job.op > MVAE_PREP_BROADCAST_ROWS ||
-                (job.op == MVAE_PREP_CONVERT_PAD && job.c < job.b) ||
-                (job.kind != MVAE_F32 && job.kind != MVAE_BF16) || (job.op == MVAE_PREP_MAKE_TABLE && !job.src2) ||
-                (job.op == MVAE_PREP_MAKE_TABLE && (job.c < 0 || job.c > 2 || (job.c == 1 && (job.b % 32)) || (job.c == 2 && (job.b % 256)))) ||
-                (job.op == MVAE_PREP_ZERO && job.kind == MVAE_BF16 && (((size_t)job.a * job.b) & 1)))
-                return MVAE_E_ARG;
-            if (job.op == MVAE_PREP_PACK_RECURRENT) {
-                const int K = job.c == 0 ? job.a : job.b, KG = job.kind == MVAE_BF16 ? 32 : 4;     // as mvae_pack_recurrent
-                if (job.a <= 0 || (job.a % 16) || (job.b % 16) || (K % KG)) return MVAE_E_ARG;
-            }
             pb.jobs[j] = job;
             // workgroups of the job: ~2048 output elements each, between 1 and 64
             size_t out = (size_t)(job.a > 0 ? job.a : 1) * (size_t)(job.b > 0 ? job.b : 1);
@@ -817,8 +830,9 @@ extern "C" int mvae_add_time_reversed(void* dst, const void* a, const void* b, i
 }
 extern "C" int mvae_scalars_accumulate(float* acc, const float* x, int32_t n, float alpha, uint32_t plain_mask, void* stream) {
     if (!acc || !x || n < 0 || n > 32) return MVAE_E_ARG;
-    if (n) hipLaunchKernelGGL(scalars_accumulate_k, dim3(1), dim3(32), 0, reinterpret_cast<hipStream_t>(stream), acc, x, n, alpha,
-                              plain_mask);
+    if (n == 0) return MVAE_OK;
+    hipLaunchKernelGGL(scalars_accumulate_k, dim3(1), dim3(32), 0, reinterpret_cast<hipStream_t>(stream), acc, x, n, alpha,
+                       plain_mask);
     MVAE_CHECK_LAUNCH();
     return MVAE_OK;
 }
@@ -826,9 +840,9 @@ extern "C" int mvae_copy2d_f32(float* dst, int32_t ldd, const float* src, int32_
                                int32_t zero_rows, void* stream) {
     if (!dst || !src || rows < 0 || cols < 0 || ldd < cols || lds < cols || zero_rows < 0 || src_row0 + zero_rows < 0)
         return MVAE_E_ARG;
-    if (rows && cols)
-        hipLaunchKernelGGL(copy2d_f32_k, dim3(nblocks((size_t)rows * cols)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), dst,
-                           ldd, src, lds, rows, cols, src_row0, zero_rows);
+    if (!rows || !cols) return MVAE_OK;
+    hipLaunchKernelGGL(copy2d_f32_k, dim3(nblocks((size_t)rows * cols)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), dst,
+                       ldd, src, lds, rows, cols, src_row0, zero_rows);
     MVAE_CHECK_LAUNCH();
     return MVAE_OK;
 }

@@ -578,9 +578,8 @@ int mvae_rnn_fwd_resident(const mvae_rnn_fwd_args& a, hipStream_t s);
 int mvae_rnn_bwd_resident(const mvae_rnn_bwd_args& a, hipStream_t s);
 
 extern "C" int mvae_rnn_fwd(const mvae_rnn_fwd_args* a, void* stream) {
-    if (!a || !a->u_pack || a->T <= 0 || a->B <= 0) return MVAE_E_ARG;
+    if (!a || mvae_check_rnn_fwd(*a) != MVAE_OK) return MVAE_E_ARG;
     // time-pipelined stacks: only the slot-interleaved kernels (seq_layout TILE16P) poll / publish
-    if (a->chunk_steps < 0 || ((a->wait_ready || a->signal_done) && a->chunk_steps == 0)) return MVAE_E_ARG;
     if ((a->wait_ready || a->signal_done) && a->seq_layout != MVAE_TILE16P && a->seq_layout != MVAE_TILE16Q) return MVAE_E_UNSUPPORTED;
     if (a->wait_ready && a->xmode != MVAE_X_DENSE) return MVAE_E_ARG;
     // the forward kernels request their inputs one (LSTM) or two (GRU) steps ahead and wait for a chunk at most once per chunk:
@@ -600,8 +599,7 @@ extern "C" int mvae_rnn_fwd(const mvae_rnn_fwd_args* a, void* stream) {
 }
 
 extern "C" int mvae_rnn_bwd(const mvae_rnn_bwd_args* a, void* stream) {
-    if (!a || !a->ut_pack || !a->hs || !a->acts || !a->da || a->T <= 0 || a->B <= 0) return MVAE_E_ARG;
-    if (a->chunk_steps < 0 || ((a->wait_ready || a->signal_done) && a->chunk_steps == 0)) return MVAE_E_ARG;
+    if (!a || mvae_check_rnn_bwd(*a) != MVAE_OK) return MVAE_E_ARG;
     if ((a->wait_ready || a->signal_done) && a->seq_layout != MVAE_TILE16P && a->seq_layout != MVAE_TILE16Q) return MVAE_E_UNSUPPORTED;
     if (a->wait_ready && !a->dhs_ext) return MVAE_E_ARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -617,7 +615,7 @@ extern "C" int mvae_rnn_bwd(const mvae_rnn_bwd_args* a, void* stream) {
 
 extern "C" int mvae_pack_recurrent(const float* U, void* out, int32_t cell, int32_t H, int32_t dtype,
                                    int32_t direction, void* stream) {
-    if (!U || !out || (H % 64) != 0 || direction < 0 || direction > 1) return MVAE_E_ARG;
+    if (!U || !out || H <= 0 || (H % 64) != 0 || direction < 0 || direction > 1) return MVAE_E_ARG;
     if (cell != MVAE_GRU && cell != MVAE_LSTM && cell != MVAE_RNN) return MVAE_E_ARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int GH = mvae_gates(cell) * H;

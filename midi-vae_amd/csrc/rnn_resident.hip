@@ -2215,6 +2215,8 @@ int mvae_rnn_bwd_multi_w8(const mvae_rnn_bwd_args* problems, int32_t n, void* st
 extern "C" int mvae_rnn_fwd_multi(const mvae_rnn_fwd_args* problems, int32_t n, const mvae_xpand_args* xpand, int32_t n_xpand,
                                   void* stream) {
     if (!problems || n <= 0 || n > RM_MAX || n_xpand < 0 || n_xpand > RM_XP_MAX || (n_xpand && !xpand)) return MVAE_E_ARG;
+    for (int i = 0; i < n; ++i)
+        if (mvae_check_rnn_fwd(problems[i]) != MVAE_OK) return MVAE_E_ARG;
     if (problems[0].seq_layout == MVAE_TILE16Q) return mvae_rnn_fwd_multi_w8(problems, n, xpand, n_xpand, stream);
     rnn_fwd_multi m;
     memset(&m, 0, sizeof(m));
@@ -2258,6 +2260,8 @@ extern "C" int mvae_rnn_fwd_multi(const mvae_rnn_fwd_args* problems, int32_t n, 
 }
 extern "C" int mvae_rnn_bwd_multi(const mvae_rnn_bwd_args* problems, int32_t n, void* stream) {
     if (!problems || n <= 0 || n > RM_MAX) return MVAE_E_ARG;
+    for (int i = 0; i < n; ++i)
+        if (mvae_check_rnn_bwd(problems[i]) != MVAE_OK) return MVAE_E_ARG;
     if (problems[0].seq_layout == MVAE_TILE16Q) return mvae_rnn_bwd_multi_w8(problems, n, stream);
     rnn_bwd_multi m;
     memset(&m, 0, sizeof(m));
