@@ -26,6 +26,7 @@ from . import hiplib as hl
 from . import ops
 from . import plan
 from . import sampling
+from .knobs import schedule_knobs
 from .layout import ModelSpec, ParamLayout, init_params
 
 from .engine_io import ArrayStaging, Results
@@ -37,14 +38,6 @@ from .engine_steps import TrainSteps
 from .engine_buffers import Buffers, _Rec, _Head, _Aux        # noqa: F401  (the records of the layer description)
 from .slots import *        # noqa: F401,F403  (scalar slots S_*, N_SCALARS, X_EXT)
 from .slots import N_SCALARS, X_EXT, X_GATHER2
-
-
-class _NullCtx(object):
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
 
 
 class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, ParamGradients, TrainSteps, Results):
@@ -70,6 +63,12 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
         self.gru_w8 = os.environ.get("MVAE_GRU_W8", "1") != "0"
         self.lay = hl.TILE16 if self.tile16 else hl.ROWMAJOR          # what the GEMM epilogues write (xp, dX)
         self.maxB = (int(max_batch) + 15) // 16 * 16
+        # the schedule knobs (knobs.py: defaults and the measurements behind them) - plain attributes a caller may change on the live
+        # engine; the dict's names key the step plans (engine_plan._plan_state)
+        self.knobs = schedule_knobs(spec, self.maxB)
+        self.knobs["index_dense"] = type(self).INDEX_DENSE      # (a class attribute: the buffers it needs are allocated here)
+        for name, value in self.knobs.items():
+            setattr(self, name, value)
         self.layout = self._make_layout()
         self._plan_init()      # step plans + the event ring behind _fork / _join (engine_plan.py)
         self.prof = None       # dict -> per-kernel HIP-event pairs are recorded on the launch stream (bench.py)
@@ -108,93 +107,25 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
                 self.s_grad2 = torch.cuda.Stream()      # second gradient stream: input-kernel / bias gradients
                 self.s_layer = [torch.cuda.Stream() for _ in range(nl)]
                 self.s_proj = [self._own_queue_stream() for _ in range(nl)]     # x*W / dX of pipelined stacks
-        self.multi_stream = True
         self._prefork = None
         self._branches_stay_forked = False
-        self.lean_sync = True            # fork / join with one packet on the critical queue (settled: r01 9.3 -> 8.86 ms; an attribute for tests)
         self._bucket_hook = None         # data parallel: dp.BucketedAllReduce of the running train_step
         self.s_comm = None               # ... and the stream its early bucket starts on (created on first use)
         self.status_allreduce = None     # data parallel: MAX of the pipeline status word over the ranks (dp.DataParallel)
-        # Stacked layers are pipelined over TIME CHUNKS: layer l runs chunk k (on its own stream) as soon as layer l-1
-        # has produced it, instead of waiting for the whole sequence.  The f32 state is carried across launches.
-        self.time_chunks = 4
-        # ... and where the slot-interleaved LSTM / GRU kernels apply AND the stack's kernels fit on the chip together
-        # (_pipelined), as ONE launch per layer with device-side hand-over every pipe_chunk time steps (no relaunch, no weight
-        # reload, layers pipe_chunk steps apart instead of T/4)
+        # time-pipelined stacks as ONE launch per layer with device-side hand-over every pipe_chunk time steps (knobs.py)
         self.pipeline = os.environ.get("MVAE_PIPELINE", "1") == "1"     # (0: one launch per (layer, chunk), e.g. several processes on ONE GPU)
         if getattr(self, "_serial_queues", False) or (share is not None and not share.pipeline and getattr(share, "_serial_queues", False)):
             self.pipeline = False
-        # time steps per hand-over: a hand-over costs every workgroup a drained vmcnt and a counter, the persistent GEMM a wait - the
-        # bigger the batch, the more rows a chunk should carry (A/B r02: 256 windows 8 / 16 / 32 / 64 -> 8.18 / 8.08 / 8.13 / 8.31 ms;
-        # 512 windows, T=2048: 35.7 / 34.5 / 35.4 at 16 / 32 / 64; decode of 1024 windows: 57.0 / 58.9 / 60.1 / 59.9 k at 16 / 32 / 64 / 128)
-        self.pipe_chunk = 16 if self.maxB <= 256 else 32 if self.maxB <= 512 else 64
-        while self.pipe_chunk > 16 and spec.T % self.pipe_chunk:
-            self.pipe_chunk //= 2
-        # the HOST is held at these points of a train step until the device has reached them (_pace: bit 2 in front of the backward
-        # pass, 4 in front of the encoder BPTT; 1 in front of the decoder forward): a device whose queues already hold the packets of
-        # the later phases - value waits on a dozen queues - runs the current phase slower.  T = 64: 1.71 -> 1.45 ms per step with
-        # 6, configs[1] 6.65 -> 6.57 (profiles/r05_c_steps_in_flight.txt); a replayed step is split into call ranges there
-        self.pace_mask = 6
-        # ... of a step enqueued in TWO calls (train_step_begin / train_step_finish: model.Autoencoder.fit, whose host converts the
-        # next minibatch - or the caller's next song - between two steps): only the pause in front of the backward pass.  A host that
-        # is held until the encoder BPTT starts comes back too late for that work: `python vae_training.py` at default settings
-        # 58 k -> 71 k windows/s end to end (no pause at all: 75 k, but configs[1] GRU fit 5.8 -> 7.6 ms per step); fit at configs[1]
-        # LSTM 7.9-8.1 -> 7.2-7.7 ms per 256-window step, GRU 5.64 -> 5.80 (profiles/r05_t_pace_mask_by_caller.txt)
-        self.pace_mask_split = 2
-        self._pace_mask_now = self.pace_mask
-        self.pace_early = True            # (engine_steps._pace_point: the pauses end when the device reaches an EARLIER point of the queue)
-        self._pace_events, self._pace_recorded = {}, set()
-        self.gate_pipe_gemms = False      # (engine_phases._launch_pipe_gemms: measured, off)
-        self.pipe_gemm_blocks = 64       # persistent grid of the dX GEMM between two pipelined layers (backward)
-        # ... and of the forward projection x*W + b: the weights-stationary kernel (csrc/gemm.hip proj_ws_k) wants a multiple of
-        # 8 XCDs x (G*H / 128) column tiles - one workgroup per (XCD, column tile) keeps its weight panel in LDS for the whole launch:
-        # 64 for LSTM, 48 for GRU.  (Round 1's kernel reloaded the panel per tile; decoder inference at 1024 windows was bound by it:
-        # 8.2 us per decoder step at 64 workgroups, 6.2 at 128 - 4.1 now at 64)
-        self.pipe_proj_blocks = 8 * max(spec.GH // 128, 1)
+        self._pace_events, self._pace_recorded = {}, set()      # (the host pauses of a train step: engine_steps._pace, _pace_point)
         # Parameter-gradient GEMMs once per layer (after its BPTT), NOT per time chunk: throughput GEMMs running beside the
         # latency-bound recurrences slow those down by more than the tail they would save.
         self._grads_clean = False
-        self.fuse_head_bwd = True        # d(h sequence) of the output Denses from the head launch (mvae_head wc / dhs)
-        self.fuse_bias_grad = True       # bias gradients from the recurrent-kernel gradient GEMM's pass over da (mvae_gemm colsum_b)
-        self.fused_latent = True         # Dense chain around the latent as one launch each way (csrc/latent.hip)
-        # Encoder stack (the LAST recurrence phase of a step): its weight-gradient GEMMs FOLLOW the running BPTT kernels chunk by chunk
-        # (mvae_gemm k_wait: one resident workgroup per (output tile, K partition) accumulates in registers over all chunks) - what
-        # is left when the recurrence ends is one chunk's share instead of four whole GEMMs (0.55 ms of the 0.77 ms tail).  All of
-        # them are ONE launch (mvae_gemm_kstream_multi) on the second gradient queue - a queue each cost more than the tail saved -
-        # and the other gradient work of that phase (velocity / instrument encoders) goes to the first one.
-        # kstream_wgs workgroups per GEMM: they wait beside the recurrences, one per CU (_kstream_ok: residency).
-        # SHORT sequences (the reference's shipped T = 64, settings.py:108-109): every weight-gradient GEMM is a 20-120 us launch
-        # that is mostly fill and drain, a dozen of them beside and behind the recurrences were two thirds of what followed the last
-        # BPTT, and their workgroups kept the recurrent launches (one workgroup per EMPTY CU) waiting for a place.  Up to
-        # defer_grads_rows rows (T x padded batch) per sequence they are collected during the backward pass and leave as ONE launch
-        # (mvae_gemm_multi) on the critical queue behind the last recurrence (_wgemm / _flush_deferred_gemms); above that the
-        # GEMMs are long enough to be worth running beside the recurrences.  (profiles/r05_c_*; 0 = never)
-        # Measured on T = 64 with the host paced (steps_in_flight / pace_mask below): 256 windows GRU 2.07 -> 1.47 ms per step, LSTM
-        # 1.72 -> 1.69; 64 windows GRU 1.46 -> 1.18
-        self.defer_grads_rows = int(os.environ.get("MVAE_DEFER_GRADS_ROWS", "32768"))
-        # ... the decoder side's (and the latent block's) BESIDE the encoder BPTT launch, on the gradient queue, released by that
-        # launch's first published chunk (_flush_deferred_gemms(early=...)): reference shape GRU 1.46 -> 1.39 ms, LSTM 1.705 -> 1.70;
-        # from defer_early_rows rows per sequence (192 windows x 64 steps: 1.525 -> 1.46; 128 windows 1.324 -> 1.327; 64: 1.17 -> 1.18)
-        self.defer_early, self.defer_early_rows = True, 12288
-        # ... with K split further until a launch has about this many workgroups (_flush_deferred_gemms): at T*B = 16384 rows the
-        # usual split (2) makes ~150 workgroups of 128 k tiles each.  0 / 256 / 384 / 512 / 1024: GRU 1.405 / 1.39 / 1.40 / 1.338 / 1.383
-        # ms per step at the reference's shape, LSTM 1.70-1.71 throughout
-        self.defer_split_wgs = 512
         self._deferred_gemms, self._deferred_small = None, []
-        self.kstream_grads = os.environ.get("MVAE_KSTREAM_GRADS", "1") == "1"
-        # (GRU: 3 GEMMs per layer -> 8 problems in the encoder launch.  Round 5, 256 windows T=512: 24 workgroups each = 192 resident
-        #  beside the 64 of the recurrences left the decoder side's held-back GEMMs no CU - 5.66 ms per step; 20 / 16 / 14 / 12:
-        #  5.42 / 5.43 / 5.36 / 5.34-5.39 (12-15 = one workgroup per output tile: under a tracer they fall 0.26 ms behind the BPTT);
-        #  <= 10: a workgroup owns two tiles and streams the second one after the BPTT: 6.13.  LSTM: 16 / 24 / 32 all 6.53, <= 12: 7.27)
-        self.kstream_wgs = 16 if spec.cell == "GRU" else 32
-        self.kstream_max_B = 256
-        self.flush_before_join = True     # (engine.backward: the encoder's collected GEMMs in front of the gradient queues' joins)
-        # k rows per workgroup and chunk of a K-streaming GEMM (0: the round-2 rule, kstream_wgs workgroups per GEMM whatever its tile
-        # count).  Round 6, same box: GRU 4.84 -> 4.69 ms per step, LSTM 6.29 -> 6.28; 1024 rows: GRU 4.94 (profiles/r06_k_kstream_rows.txt)
-        self.kstream_rows = 2048
-        self.dec_kstream = True           # the decoder notes stack's too (engine_phases._notes_backward_multi, _dec_kstream_ok)
-        self.hold_side_heads, self._hold_side = True, False
-        self.kstream_singles = True      # (settled r02: LSTM 7.60 -> 7.50 ms, GRU 6.55 -> 6.38)    # ... and the dU GEMM of a full-length single-layer encoder branch
+        # The decoder notes stack's weight gradients are a K-streaming launch too (_decoder_kstream_ok), the side heads' gradient
+        # GEMMs are held behind the latent chain beside it (_hold_side, armed in backward), and the dU GEMM of a full-length
+        # single-layer encoder branch joins the encoder's K-streaming launch (settled r02: LSTM 7.60 -> 7.50 ms, GRU 6.55 -> 6.38;
+        # profiles/r02_n_ab_kstream_gradients.txt)
+        self._hold_side = False
         self._kstream_extra = None
         self._grad_streams = None        # (s_grad, s_grad2) unless overridden for a phase
         self._n_side = 0                 # recurrences running beside the stack being scheduled (residency, _pipelined)
@@ -206,36 +137,18 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
         self._hist_fused = None          # train step whose history comes out of its own encoder forward (model.py: fused pre-pass)
         self._redo_hist = None           # ... kept until the step is verified (_redo_step)
         self._fused_dst = None           # (caller's rows, engine buffer) of a fused pre-pass whose z' is still to be handed over
-        # the recurrences of a phase as ONE launch on the critical queue instead of one launch per queue (engine_phases.py)
+        # the recurrences of a phase as ONE launch on the critical queue instead of one launch per queue (engine_phases.py), up to
+        # phase_max_B windows (knobs.py)
         self.phase_multi = True
-        # ... up to this many (padded) windows per call: measured (profiles/r03_j_*) 256 windows -6 % (LSTM) / -9 % (GRU) per train
-        # step, but 512 windows at T=2048 +6.5 % and decoding 1024 windows +4 % - there the recurrences themselves fill the chip
-        # and the per-queue launches (producers dispatched first) place them better than one launch's index order
-        self.phase_max_B = 256
-        # (_index_as_dense; measured r03_r: GRU step -0.07 ms, LSTM +0.09 ms - there the bottom layer does not set the pace)
-        #  Round 4: the indexed kernels gather tile PAIRS from a paired-column table (8 x 16 bytes per row and step instead of 16 x 8:
-        #  LSTM 2.66 -> 2.17, GRU 2.06 -> 1.70 us per step alone - faster than a dense input) and the written-out rows lose on both
-        #  cells (GRU 5.71 vs 5.63 ms per step, LSTM 7.11 vs 6.91: profiles/r04_l_index_dense_ab.txt): off by default
-        self.index_dense = type(self).INDEX_DENSE      # (a class attribute: the buffers it needs are allocated here)
-        self.index_dense_blocks = 16
-        self.xpand_blocks = 16
-        self.gate_side_heads = True      # (settled r03_z: -0.03 ms)   # (decoder_forward: counter instead of event)
         self._last_stack_gate = None
-        # (_head_forward: inference on per-queue pipelined stacks.  profiles/r03_zz_decode_head_slices.txt: decode configs[4] LSTM
-        #  -3..5 % with 2 slices, -1..3 % with 4; GRU -3 % / -6..7 %: the slices take memory bandwidth from the recurrences they follow)
-        self.head_slices = 2 if spec.cell == "LSTM" else 4
         self._top_publish = None
         # (_join; r03_z: -0.02 / -0.04 ms.  NOT when kernels are run one at a time - rocprofv3 counter collection: a critical queue parked
         #  in a value wait and a writer queue held back behind it never finish; event joins work there)
         serial = getattr(self, "_serial_queues", False) or (share is not None and getattr(share, "_serial_queues", False))
         self.value_join = not serial and len(self.s_proj) > 0     # (no stacked layer: no probe was run)
         self._join_seq = {}
-        self._diag_no_param_grads = os.environ.get("MVAE_DIAG_NO_PARAM_GRADS", "0") == "1"
-        # (_grad_portions) -1: by the rows of the sequence (4 portions from 2^20 rows, none below 2^19), 0: off, N: N portions
-        self.grad_portions = -1
         self._grad_portion_jobs = None
         self._single_slot, self._single_slot_end = 0, 3
-        self._hold_dec_grads = 1     # (engine_phases._notes_backward_multi; A/B r03_j: LSTM -0.06 ms, GRU neutral)
         self._after_chain = None
         self._tail_streams = []          # queues besides the two gradient queues that carry gradient work of the running step
         if share is None:
@@ -352,37 +265,36 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
 
     # ---- stream helpers -------------------------------------------------------------------------------------
     def _fork(self, *streams):
+        """``streams`` wait for everything enqueued so far on the current one.  Forks and joins put ONE packet on the critical queue
+        however many streams branch off or come back (settled in round 1 against one event and one wait per stream: 9.3 -> 8.86 ms
+        per step)"""
         if self._prefork is not None and self._prefork[0] == torch.cuda.current_stream() and \
                 all(any(st is p for p in self._prefork[1]) for st in streams):
             for st in streams:              # already forked by _fork_with_stack
                 self._prefork[1].remove(st)
             return
-        cur = torch.cuda.current_stream()
-        if self.lean_sync and len(streams) > 1:
-            ev = self._ev_record(cur)       # ONE marker packet on this queue, however many streams branch off
+        if streams:
+            ev = self._ev_record(torch.cuda.current_stream())       # ONE marker packet on this queue, however many streams branch off
             for st in streams:
                 self._ev_wait(st, ev)
-            return
-        for st in streams:
-            self._wait_stream(st, cur)
 
     def _fork_with_stack(self, layers, *streams, also=()):
         """fork ``streams`` AND the streams a pipelined stack over ``layers`` will use (and ``also``) with one event; the
         forks the callees then ask for from THIS stream for those streams are skipped, once each (nothing they depend on
         may be launched on the current stream in between; the caller clears ``_prefork`` after the stack)."""
         extra = ()
-        if self.lean_sync and self._pipelined(layers):
+        if self._pipelined(layers):
             L = len(layers)
             extra = (*self.s_layer[:L - 1], *self.s_proj[:L - 1], *also)
         self._fork(*streams, *extra)
         self._prefork = (torch.cuda.current_stream(), list(extra)) if extra else None
 
     def _join(self, *streams, word=None):
-        """the current stream waits for ``streams``.  ``word`` (an index into the engine's join words; MVAE_VALUE_JOIN=1): the last
+        """the current stream waits for ``streams``.  ``word`` (an index into the engine's join words; ``value_join``): the last
         hop is a value written behind the side queue's work (hipStreamWriteValue32) and waited for here (hipStreamWaitValue32)
         instead of an event record + a barrier packet on that event"""
         cur = torch.cuda.current_stream()
-        if word is not None and self.value_join and self.multi_stream and streams:
+        if word is not None and self.value_join and streams:
             for a, b in zip(streams, streams[1:]):
                 self._wait_stream(b, a)
             self._join_seq[word] = seq = self._join_seq.get(word, 0) + 1
@@ -395,15 +307,12 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
             ops.stream_write_value32(w, seq, stream=streams[-1])
             ops.stream_wait_value32(w, seq, stream=cur)
             return
-        if self.lean_sync and len(streams) > 1:
+        if streams:
             # chained: every side queue takes its barrier packet when ITS work ends; the joining queue (the critical one)
             # processes one barrier packet instead of len(streams)
             for a, b in zip(streams, streams[1:]):
                 self._wait_stream(b, a)
             self._wait_stream(cur, streams[-1])
-            return
-        for st in streams:
-            self._wait_stream(cur, st)
 
     def _join_into(self, stream):
         """``stream`` waits for everything enqueued so far on the current stream and on every side stream"""
@@ -420,9 +329,6 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
         ordered after everything enqueued so far on the current stream.  While a list is collecting (``_deferred_side``: the
         phase launch that follows releases the work by a device counter - an event record here is one more packet, ~30 us, on
         the critical queue) the work is only noted."""
-        if not self.multi_stream:
-            fn()
-            return
         if self._deferred_side is not None:
             self._deferred_side.append(fn)
             return
@@ -431,8 +337,8 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
             fn()
 
     def _on(self, stream):
-        """context: run on ``stream`` (or stay on the current one when multi-stream execution is off)"""
-        return torch.cuda.stream(stream) if self.multi_stream else _NullCtx()
+        """context: run on ``stream``"""
+        return torch.cuda.stream(stream)
 
     def _timed(self, key, fn, steps=0):
         """Run ``fn`` (one kernel launch); when profiling, bracket it with HIP events on the launch stream.
@@ -553,7 +459,7 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
     # ------------------------------------------------------------------------------------------------------
     def _nchunks(self, layers):
         T = layers[0].T
-        n = self.time_chunks if (len(layers) > 1 and self.multi_stream) else 1
+        n = self.time_chunks if len(layers) > 1 else 1
         while n > 1 and (T % n or (T // n) < 16):
             n -= 1
         return n
@@ -658,7 +564,7 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
         if len(layers) < 2:
             return False
         T = layers[0].T
-        return (self.pipeline and self.multi_stream and len(layers) - 1 <= len(self.s_layer) and T % self.pipe_chunk == 0 and
+        return (self.pipeline and len(layers) - 1 <= len(self.s_layer) and T % self.pipe_chunk == 0 and
                 len(layers) * 2 * (T // self.pipe_chunk) <= 1024 and
                 all(self._il(r) for r in layers) and
                 self._resident_cus(layers, self._cur_B) <= self.num_cus)
@@ -853,25 +759,22 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
         aux_src = {a.src for a in self.aux}
         self._cur_B, self._n_side = B, len(side)
         multi = len(self.dec_notes) > 1 and self._phase_ok(self.dec_notes, ())      # (the notes stack is ONE launch on this queue)
-        if multi and side and self.gate_side_heads:
+        if multi and side:
             # the side heads leave the critical queue WITHOUT an event (a record is a packet of ~50 us between the latent chain and the
             # decoder launch): their queues wait for the first chunk the notes stack publishes - it runs behind the latent chain
+            # (settled against an event fork, r03_z: -0.03 ms per step)
             self._last_stack_gate = None
             self._head_forward(self.head["notes"], B, Breal, states, tg, want_probs or "notes" in aux_src, slot=1)
             assert self._last_stack_gate is not None, "the notes stack did not run as a phase launch"
             word, value = self._last_stack_gate
             for h in side:
                 ops.stream_wait_value32(word, value, stream=h.stream)
-        else:
-            if multi:
-                if side:
-                    self._fork(*[h.stream for h in side])
-            else:
-                self._fork_with_stack(self.dec_notes, *[h.stream for h in side])
+        elif not multi:
+            self._fork_with_stack(self.dec_notes, *[h.stream for h in side])
         for h in side:
             with self._on(h.stream):
                 self._head_forward(h, B, Breal, states, tg, want_probs or h.name in aux_src or (h.kind == 1 and self._want_vel), slot=None)
-        if not (multi and side and self.gate_side_heads):
+        if not (multi and side):
             self._head_forward(self.head["notes"], B, Breal, states, tg, want_probs or "notes" in aux_src, slot=1)
         self._prefork = None
         self._n_side = 0
@@ -1131,7 +1034,7 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
 
     def _fused_head_bwd(self, name, tg):
         """extra arguments of ops.head: the gradient w.r.t. the top cell's h sequence comes out of the head launch itself"""
-        if not (self.training and tg and self.fuse_head_bwd and self.lay == hl.TILE16 and self.spec.H <= 256):
+        if not (self.training and tg and self.lay == hl.TILE16 and self.spec.H <= 256):
             return {}
         if any(a.src == name or a.key == name for a in self.aux):     # (d(logits) of that head changes after its launch)
             return {}
@@ -1204,7 +1107,7 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
         # (data parallel with the early bucket - _bucket_hook - : every decoder-side gradient has to be QUEUED when the bucket's
         #  collective is issued, in front of the encoder launch: nothing is held back behind it then -
         #  test_nothing_is_added_to_the_decoder_bucket_after_its_collective_was_issued)
-        early_bucket = self._bucket_hook is not None and self.multi_stream and self.layout.dec_begin > 0
+        early_bucket = self._bucket_hook is not None and self.layout.dec_begin > 0
         self._after_chain = [] if (notes_multi and not self.enc_bi and len(self.enc_notes) > 1 and not early_bucket and
                                    self._phase_ok(self.enc_notes, [r for r, _, _ in self.enc_meta])) else None
         if self._branches_stay_forked:      # (train step: the side heads' queues go straight on with their own backward)
@@ -1215,9 +1118,9 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
                 self._fork(*[h.stream for h in side])
         else:
             self._fork_with_stack(self.dec_notes, *[h.stream for h in side], also=(self.s_grad,))
-        if notes_multi and self._dec_kstream_ok(self.dec_notes, B):
+        if notes_multi and self._decoder_kstream_ok(self.dec_notes, B):
             self._grad_streams = (self.s_grad, self.s_grad)      # the second gradient queue holds the notes stack's K-streaming launch
-            self._hold_side = self.hold_side_heads
+            self._hold_side = True
         for h in side:
             with self._on(h.stream):
                 self._head_stack_backward(h, B, dstates, slot=None)
@@ -1243,7 +1146,7 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
         ldc = self.ncat * H
         self._mark("  latent block backward")
         hook = self._bucket_hook
-        if hook is not None and self.multi_stream and self.layout.dec_begin > 0:
+        if early_bucket:
             # data parallel: every decoder-side gradient [dec_begin, total) is queued by now - start its all-reduce on the
             # communication stream, beside the encoder BPTT (dp.BucketedAllReduce)
             if self.s_comm is None:
@@ -1267,7 +1170,7 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
             for k, (r, st, src) in enumerate(self.enc_meta, 1):
                 with self._on(st):
                     inp = (dict(xs=self._v(src, r.T, B)) if r.xmode == hl.X_SCALAR else dict(idx=self._v(src, r.T, B)))
-                    follow = (ks_extra is not None and not ks_extra and self.kstream_singles and r.T == T and
+                    follow = (ks_extra is not None and not ks_extra and r.T == T and
                               self._il(r) and r.xmode != hl.X_CONST and
                               (2 if s.cell == "GRU" else 1) + (3 if s.cell == "GRU" else 2) * len(self.enc_notes) <= 8)
                     self._stack_backward([r], B, dh_last=dcat[:, k * H:(k + 1) * H], dh_last_ld=ldc,
@@ -1302,7 +1205,7 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
 
     def _defers_grads(self, B):
         """does a step of B (padded) windows collect its weight-gradient GEMMs for one launch behind the last recurrence?"""
-        return bool(self.training and self.tile16 and self.multi_stream and 0 < self.spec.T * B <= self.defer_grads_rows)
+        return bool(self.training and self.tile16 and 0 < self.spec.T * B <= self.defer_grads_rows)
 
     def _latent_chain_backward(self, Breal, B):
         """The same as ONE launch (csrc/latent.hip) followed by the parameter-gradient GEMMs on the side streams; None if

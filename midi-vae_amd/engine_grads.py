@@ -30,13 +30,6 @@ def kstream_parts(tiles, chunk_rows, kstream_rows, kstream_wgs):
         P *= 2
     return P
 
-class _NullCtx(object):
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
-
 
 class ParamGradients(object):
     def _grad_portions(self, r, B, publishes):
@@ -157,7 +150,7 @@ class ParamGradients(object):
         sg1, sg2 = self._grad_streams or (self.s_grad, self.s_grad2)
         deferring = self._deferred_gemms is not None
         if deferring:                       # (everything below is collected: nothing is enqueued on the gradient queues now)
-            on1 = on2 = _NullCtx()
+            on1 = on2 = contextlib.nullcontext()
         else:
             on1, on2 = self._on(sg1), self._on(sg2)
             if gate is None:
@@ -168,9 +161,8 @@ class ParamGradients(object):
         # bias gradient = column sums of da: from the recurrent-kernel gradient GEMM's own pass over da (fast bf16 path) - also for
         # the decoder cells on a constant input when that input is all zeros (what the reference's packers always pass,
         # vae_definition.py:820,916: dW = start^T sum_t(da) = 0 then, and the sum over time is only needed for the bias)
-        const_fused = (r.xmode == hl.X_CONST and self.start_zero.get(p, False) and self.tile16 and self.fuse_bias_grad and
-                       not skip_dU)
-        fuse_b = (r.xmode != hl.X_CONST or const_fused) and self.tile16 and self.fuse_bias_grad
+        const_fused = (r.xmode == hl.X_CONST and self.start_zero.get(p, False) and self.tile16 and not skip_dU)
+        fuse_b = (r.xmode != hl.X_CONST or const_fused) and self.tile16
         gb = G[p + ".b"]
         with on1:
             # recurrent kernel: dU = sum_t h_{t-1}^T da_t   (GRU candidate block uses r*h_{t-1})
@@ -223,7 +215,7 @@ class ParamGradients(object):
         that may start late; at 512 windows 96: ordinary GEMMs then, as measured, profiles/r02_q_pipe_chunk_by_batch.txt.)"""
         s = self.spec
         count = (3 if s.cell == "GRU" else 2) * len(layers)      # GEMMs per layer: dU (GRU: two launches) and dW
-        if not (self.kstream_grads and self._deferred_gemms is None and self.multi_stream and self.fuse_bias_grad and self.tile16 and count <= 8 and
+        if not (self.kstream_grads and self._deferred_gemms is None and self.tile16 and count <= 8 and
                 self._pipelined(layers) and all(r.xmode in (hl.X_INDEX, hl.X_DENSE) for r in layers)):
             return False
         if B > self.kstream_max_B:       # (a chunk's rows grow with the batch, the time the BPTT takes for it does not)
@@ -243,13 +235,13 @@ class ParamGradients(object):
                 extra += max(0, wgs - self.kstream_wgs)
         return extra
 
-    def _dec_kstream_ok(self, layers, B):
+    def _decoder_kstream_ok(self, layers, B):
         """the decoder notes stack's weight gradients as a K-streaming launch behind its BPTT launch?  As _kstream_ok, for a stack
         whose bottom cell steps on a constant ALL-ZERO start row (what the reference's packers pass, vae_definition.py:820,916: its
         input-kernel gradient is zero and its bias gradient the column sums of da, fused into the dU GEMM)."""
         s = self.spec
-        if not (self.dec_kstream and self.kstream_grads and self._deferred_gemms is None and self.multi_stream and
-                self.fuse_bias_grad and self.tile16 and self._pipelined(layers) and B <= self.kstream_max_B and not self._diag_no_param_grads):
+        if not (self.kstream_grads and self._deferred_gemms is None and self.tile16 and self._pipelined(layers) and
+                B <= self.kstream_max_B and not self._diag_no_param_grads):
             return False
         bottom, rest = layers[0], layers[1:]
         if not (bottom.xmode == hl.X_CONST and self.start_zero.get(bottom.prefix, False) and all(r.xmode == hl.X_DENSE for r in rest)):

@@ -27,7 +27,7 @@ class PhaseLaunches(object):
     def _phase_ok(self, stack, singles):
         """may ``stack`` (bottom -> top) and the single-layer recurrences ``singles`` run as one launch?"""
         recs = list(stack) + list(singles)
-        return (self.phase_multi and self._cur_B <= self.phase_max_B and self.tile16 and self.multi_stream and 0 < len(recs) <= 8 and
+        return (self.phase_multi and self._cur_B <= self.phase_max_B and self.tile16 and 0 < len(recs) <= 8 and
                 all(self._il(r) for r in recs) and (len(stack) < 2 or self._pipelined(stack)) and
                 all(r.xmode != hl.X_SCALAR or self._scalar_as_dense(r) for r in recs))
 
@@ -83,7 +83,7 @@ class PhaseLaunches(object):
             if not top:
                 gemms.append((li, lambda li=li: self._rec_xp(
                     layers[li + 1], B, 0, 1, max_blocks=self.pipe_proj_blocks, chunk_rows=cs * B, chunk_wait=sync[li, 0],
-                    chunk_wait_value=hs_target, chunk_done=sync[li, 1], chunk_status=status), (sync[li, 0][0:1], hs_target)))
+                    chunk_wait_value=hs_target, chunk_done=sync[li, 1], chunk_status=status)))
         return probs, gemms
 
     def _launch_phase_forward(self, key, probs, gemms, xpands=(), steps=0):
@@ -91,19 +91,17 @@ class PhaseLaunches(object):
         a GEMM reads nothing before its producer (a problem of the launch, behind the weight preparation on this queue) has
         published a chunk, its queue orders it against the GEMMs of the other phases, and an event record would be one more packet
         (~30-50 us) on the critical queue per phase.  A GEMM that starts early polls."""
-        streams = [self.s_proj[li] for li, _, _ in gemms]
+        streams = [self.s_proj[li] for li, _ in gemms]
         ok = [True]
         self._timed(key, lambda: ok.__setitem__(0, ops.rnn_fwd_multi(probs, xpands)), steps=steps)
         assert ok[0], "mvae_rnn_fwd_multi refused a problem _phase_ok admitted"
         self._launch_pipe_gemms(gemms, streams)
 
     def _launch_pipe_gemms(self, gemms, streams):
-        """the persistent GEMMs between the layers of a phase launch, each on its queue.  (``gate``: a value wait for the first chunk
-        its producer publishes, so that the GEMM is not dispatched - resident and polling - a phase early; measured in round 5, no
-        gain: T = 64 2.045 -> 2.057 ms, T = 512 6.73 -> 6.81, profiles/r05_c_*; kept as an option for that measurement only)"""
-        for (li, fn, gate), st in zip(gemms, streams):
-            if self.gate_pipe_gemms:
-                ops.stream_wait_value32(gate[0], gate[1], stream=st)
+        """the persistent GEMMs between the layers of a phase launch, each on its queue.  (NOT behind a value wait for the first
+        chunk its producer publishes, which would keep the GEMM from being dispatched - resident and polling - a phase early:
+        measured in round 5, no gain: T = 64 2.045 -> 2.057 ms, T = 512 6.73 -> 6.81, profiles/r05_c_steps_in_flight.txt)"""
+        for (li, fn), st in zip(gemms, streams):
             with torch.cuda.stream(st):
                 fn()
 
@@ -165,11 +163,11 @@ class PhaseLaunches(object):
             if li < L - 1:
                 gemms.append((li, lambda li=li, r=r: self._rec_dx(
                     r, B, 0, 1, max_blocks=self.pipe_gemm_blocks, chunk_rows=cs * B, chunk_reverse=True, chunk_wait=sync[li, 0],
-                    chunk_wait_value=da_target, chunk_done=sync[li, 1], chunk_status=status), (sync[li, 0][nchp - 1:nchp], da_target)))
+                    chunk_wait_value=da_target, chunk_done=sync[li, 1], chunk_status=status)))
         return probs, gemms, (sync, da_target, nchp)
 
     def _launch_phase_backward(self, key, probs, gemms, steps=0):
-        streams = [self.s_proj[li] for li, _, _ in gemms]
+        streams = [self.s_proj[li] for li, _ in gemms]
         ok = [True]
         self._timed(key, lambda: ok.__setitem__(0, ops.rnn_bwd_multi(probs)), steps=steps)
         assert ok[0], "mvae_rnn_bwd_multi refused a problem _phase_ok admitted"
@@ -188,7 +186,7 @@ class PhaseLaunches(object):
             with torch.cuda.stream(self.s_grad):
                 head_grads()
         L = len(h.layers)
-        if self._dec_kstream_ok(h.layers, B):
+        if self._decoder_kstream_ok(h.layers, B):
             # The stack's weight-gradient GEMMs as ONE K-streaming launch that FOLLOWS this launch chunk by chunk (as the encoder
             # stack's do, _encoder_backward_multi): they end with the BPTT instead of starting at its end, i.e. they no longer run
             # across the latent chain - a latency-bound kernel on the critical queue that takes 2-3 times as long beside them
@@ -203,9 +201,10 @@ class PhaseLaunches(object):
                 ops.gemm_kstream_multi(problems)
             return True
         for li, r in enumerate(reversed(h.layers)):
-            if (li == L - 1 or self._hold_dec_grads >= 2) and self._hold_dec_grads and self._after_chain is not None:
+            if li == L - 1 and self._after_chain is not None:
                 # the bottom layer's da is complete when the launch ends - exactly when the latent chain (a latency-bound kernel
                 # between this phase and the next) starts: its gradient GEMMs wait for the ENCODER launch's first chunk instead
+                # (the bottom layer only, not every layer: A/B r03_j, LSTM -0.06 ms, GRU neutral)
                 self._after_chain.append(lambda r=r: dict(r=r, B=B, start=start))
             else:
                 self._rec_param_grads(r, B, start=start, gate=(sync[li, 0][0:1], da_target))
@@ -233,7 +232,7 @@ class PhaseLaunches(object):
             probs.append(self._rec_bptt(r, B, dh_last=dcat[:, k * H:(k + 1) * H], dh_last_ld=ldc, build=True,
                                         pipe=dict(chunk_steps=cs, status=status, signal_done=sync1[0, 0])))
             single_gate[r.prefix] = (sync1[0, 0][0:1], target1)
-            if (kstream and follow is None and self.kstream_singles and r.T == T and cs == self.pipe_chunk and
+            if (kstream and follow is None and r.T == T and cs == self.pipe_chunk and
                     (2 if s.cell == "GRU" else 1) + (3 if s.cell == "GRU" else 2) * len(self.enc_notes) <= 8):
                 ks1 = dict(counters=sync1[0, 0], target=target1, rows=cs * B, status=status)
                 extra = self._kstream_problems(r, B, None, ks1, only_dU=True)

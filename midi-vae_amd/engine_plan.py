@@ -28,13 +28,10 @@ class PlannedSteps(object):
     # attributes whose value decides which launches a call makes (part of the plan key) and which a call leaves changed (restored
     # after a replay to what the recorded calls left)
     _PLAN_STATE = ("_count_pending", "_grads_clean", "_dxp0_clean", "_have_targets", "_S_done", "_pipe_used", "pipeline",
-                   "multi_stream", "_have_staged_targets", "lean_sync", "value_join", "phase_multi")
-    # schedule knobs a caller (a test, an A/B script) may change on a LIVE engine: part of the plan key, so that a change selects
-    # other plans instead of replaying the launch list recorded under the old value
-    _PLAN_CONFIG = ("head_slices", "grad_portions", "index_dense",
-                    "index_dense_blocks", "xpand_blocks", "pipe_chunk", "phase_max_B", "kstream_grads", "kstream_wgs", "kstream_rows", "kstream_max_B", "flush_before_join", "dec_kstream", "hold_side_heads",
-                    "kstream_singles", "pipe_gemm_blocks", "pipe_proj_blocks", "time_chunks", "fuse_head_bwd", "fuse_bias_grad",
-                    "fused_latent", "gate_side_heads", "_hold_dec_grads", "_diag_no_param_grads", "use_plans", "defer_grads_rows", "defer_early", "defer_early_rows", "defer_split_wgs", "gate_pipe_gemms", "pace_mask", "pace_mask_split", "_pace_mask_now", "pace_early")
+                   "_have_staged_targets", "value_join", "phase_multi")
+    # The schedule knobs a caller (a test, an A/B script) may change on a LIVE engine are part of the plan key too, so that a change
+    # selects other plans instead of replaying the launch list recorded under the old value: _plan_state iterates the
+    # names of Engine.knobs, the dict the engine's attributes were set from (knobs.py) - there is no second list to keep.
     # ... and the spec's floats that reach kernel arguments as immediates of the recorded launches
     _PLAN_SPEC = ("lr", "beta", "prior_mean", "prior_std", "epsilon_std", "w_instr", "w_vel", "w_style", "w_held", "w_next", "w_sig",
                   "w_cnotes", "w_cinstr", "optimizer")
@@ -43,7 +40,6 @@ class PlannedSteps(object):
     _REBASE = 1 << 30          # device counters are re-based (synchronize + zero) before they reach this (engine._sync_region, _join)
 
     def _plan_init(self):
-        self.use_plans = os.environ.get("MVAE_PLANS", "1") == "1"
         self._plans = {}
         self._ev_pool, self._ev_i = [], 0
         self._host_results, self._ext_streams, self._plan_depth = {}, {}, 0
@@ -97,7 +93,7 @@ class PlannedSteps(object):
     def _plan_state(self):
         spec = self.spec
         return (tuple(getattr(self, n, None) for n in self._PLAN_STATE) +
-                tuple(getattr(self, n, None) for n in self._PLAN_CONFIG) +
+                tuple(getattr(self, n, None) for n in self.knobs) +
                 tuple(getattr(spec, n, None) for n in self._PLAN_SPEC) +
                 (frozenset(self._xp0_bias), tuple(sorted(self.start_zero.items())), bool(self._weights_dirty),
                  frozenset(self._pipe_verified), self._prep is None, getattr(self, "status_allreduce", None) is not None))
@@ -209,24 +205,23 @@ class PlannedSteps(object):
                 return fn()
             if params:
                 cnt.update(params)          # (the call's parameters: the real number of windows, 1 / global minibatch size)
-            if True:
-                for i, _, _ in slot.brackets:            # (their pairs are recorded again by this replay)
-                    self._prof_harvest(i)
-                if slot.plan.marks:
-                    self._plan_set_counters(slot.plan.run_ranges(cnt, self._replay_host(host or {}, slot.host_results)))
-                else:
-                    self._plan_set_counters(slot.plan.run(cnt))
-                vals, xp0, dver, dprep = slot.post
-                for n, v in zip(self._PLAN_STATE, vals):
-                    setattr(self, n, v)
-                self._xp0_bias = set(xp0)
-                self._pver[0] += dver
-                self._prepared_ver = self._pver[0] + dprep
-                for i, k, n in slot.brackets:
-                    self._prof_pending[i] = (k, n)
-                slot.runs += 1
-                self.plan_stats["replayed"] += 1
-                return None
+            for i, _, _ in slot.brackets:            # (their pairs are recorded again by this replay)
+                self._prof_harvest(i)
+            if slot.plan.marks:
+                self._plan_set_counters(slot.plan.run_ranges(cnt, self._replay_host(host or {}, slot.host_results)))
+            else:
+                self._plan_set_counters(slot.plan.run(cnt))
+            vals, xp0, dver, dprep = slot.post
+            for n, v in zip(self._PLAN_STATE, vals):
+                setattr(self, n, v)
+            self._xp0_bias = set(xp0)
+            self._pver[0] += dver
+            self._prepared_ver = self._pver[0] + dprep
+            for i, k, n in slot.brackets:
+                self._prof_pending[i] = (k, n)
+            slot.runs += 1
+            self.plan_stats["replayed"] += 1
+            return None
         if slot.dead is not None:
             return fn()
         pre, ver = self._plan_counters(), (self._pver[0], self._prepared_ver)

@@ -67,7 +67,7 @@ class TrainSteps(object):
         # The velocity / instrument branches' backward depends on nothing the notes branch does in between: no join at
         # the end of the decoder forward pass and no fork at the start of the backward pass (two packets less on the
         # critical queue); they are joined where the decoder BPTT ends.
-        self._branches_stay_forked = self.lean_sync and self.multi_stream and not self.aux
+        self._branches_stay_forked = not self.aux
         try:
             self._pace(1)
             self.decoder_forward(B)
@@ -163,7 +163,7 @@ class TrainSteps(object):
 
     def _train_step_finish(self, B, allreduce):
         self._bucket_hook = self._overlap_hook(allreduce, B)
-        self._branches_stay_forked = self.lean_sync and self.multi_stream and not self.aux
+        self._branches_stay_forked = not self.aux
         try:
             self.decoder_forward(B)
             self._pace(2)
@@ -215,7 +215,7 @@ class TrainSteps(object):
     def _pace(self, bit):
         """hold the HOST here until the device has reached the pause's point of the step (pace_mask: bit 1 before the decoder forward,
         2 before the backward pass, 4 before the encoder BPTT) - a host action of the step, so a replayed step pauses there too.
-        The point is an event of the pause's own: recorded further up the queue by _pace_point (pace_early), else here."""
+        The point is an event of the pause's own: recorded further up the queue by _pace_point, else here."""
         if self._pace_mask_now & bit:
             if bit not in self._pace_recorded:
                 self._pace_record(bit)
@@ -231,11 +231,11 @@ class TrainSteps(object):
         self._pace_recorded.add(bit)
 
     def _pace_point(self, bit):
-        """the point of the step the host pause ``bit`` waits for, when it lies BEFORE the pause (pace_early): the pause further down
+        """the point of the step the host pause ``bit`` waits for, when it lies BEFORE the pause: the pause further down
         the same queue then ends when the device gets HERE, and the host's wake-up and the first launches of the next call range
         hide behind the kernels in between (the notes head in front of the backward pass, the latent chain in front of the encoder
-        BPTT: 35-40 us of idle critical queue each, timeline r05_p)"""
-        if self._pace_mask_now & bit and self.pace_early:
+        BPTT: 35-40 us of idle critical queue each, timeline r05_p; settled in round 5, always on)"""
+        if self._pace_mask_now & bit:
             self._pace_record(bit)
 
     def _pace_now(self, bit):
