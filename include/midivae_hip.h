@@ -38,6 +38,10 @@
 extern "C" {
 #endif
 
+/* ABI 9 also carries fields APPENDED at the end of mvae_head_args (row_out), mvae_latent_fwd_args and mvae_latent_chain_fwd_args
+ * (kl_rows, style_rows): per-row loss / metric outputs, NULL = the behaviour before them.  No entry point, enum value or
+ * positional signature changed, so the version did not move - but a binding generated from an earlier copy of this header passes
+ * structs that are too short and has to regenerate them. */
 #define MVAE_ABI_VERSION 9
 
 enum { MVAE_OK = 0, MVAE_E_ARG = -1, MVAE_E_UNSUPPORTED = -2, MVAE_E_LAUNCH = -3,
@@ -336,6 +340,13 @@ typedef struct {
     const uint8_t* target_idx2;   /* kind 0, or NULL: (R) the SECOND hot column of a two-hot target row (attach_instruments,
                                      reference import_midi.py:288-292: pitch one-hot | instrument one-hot), 255 = none:
                                      loss -log p[t1] - log p[t2], accuracy against the first hot column             */
+    float* row_out;               /* (R,2) f32 or NULL (appended under ABI 9): the addends of every row r < R of this launch, as
+                                     plain stores by the row's one writer - row_out[2r] what the row adds to scalars[0] (kind 0:
+                                     rw*ce, kind 1: rw*(p-y)^2), row_out[2r+1] what it adds to scalars[1] (1.0f or 0.0f; rows with
+                                     b >= b_valid: 0).  Written with or without scalars, probs, want_grad or dhs; every other
+                                     output is bit-identical to the launch without it.  A sliced launch passes the pointer to
+                                     its own first row, as for dlogits.  Per-window losses: mvae_sum_over_time(row_out, MVAE_F32,
+                                     T, 2*B, ...) over the (T, B, 2) block of a time-major launch                          */
 } mvae_head_args;
 int mvae_head(const mvae_head_args* a, void* stream);
 /* padded column count NP used for `wt` rows and `dlogits` columns of an N-wide head: 16 / 32 / 64 / 128 for N <= 128,
@@ -397,6 +408,9 @@ typedef struct {
     float* scalars;               /* (3): += inv_batch*sum_b kl_b, += sum_b rw*style CE, += style argmax hits */
     int32_t ldz;                  /* row stride of z (0 = Z, else >= Z): z may be the left block of [z | history].
                                      With style_target: 1 <= C <= 64 and C <= Z (MVAE_E_ARG)                  */
+    float* kl_rows;               /* (B) or NULL (appended under ABI 9): row b's addend to scalars[0], a plain store        */
+    float* style_rows;            /* (B,2) or NULL (appended under ABI 9): row b's addends to scalars[1] and scalars[2];
+                                     written only where the style head runs (style_target and C > 0)                       */
 } mvae_latent_fwd_args;
 int mvae_latent_fwd(const mvae_latent_fwd_args* a, void* stream);
 
@@ -438,6 +452,9 @@ typedef struct {
     float* style_probs;           /* (B,C) out or NULL                                                       */
     float* scalars;               /* (3) as mvae_latent_fwd_args                                             */
     float* S;                     /* (B,n_init) out                                                          */
+    float* kl_rows;               /* (B) or NULL (appended under ABI 9): row b's addend to scalars[0]; rows >= B_valid hold 0 */
+    float* style_rows;            /* (B,2) or NULL (appended under ABI 9): row b's addends to scalars[1] and scalars[2], rows
+                                     >= B_valid 0; written only where the style head runs (style_target and C > 0)         */
 } mvae_latent_chain_fwd_args;
 int mvae_latent_chain_fwd(const mvae_latent_chain_fwd_args* a, void* stream);
 

@@ -35,7 +35,10 @@ __device__ __forceinline__ f32x4 frag_from<float>(const float* src, bool valid) 
 template <typename WT, int NTL, int KIND>
 __host__ __device__ constexpr int head_rb() { return (sizeof(WT) == 2 && KIND == 0 && NTL <= 4) ? 2 : 1; }
 
-template <typename WT, int NTL, int KIND>
+// ROWS: the launch keeps every row's two addends (a.row_out).  An instantiation of its own: the softmax kernels of the wide heads sit
+// at their register limit, and one more store in their row loop - taken or not - cost the 61-column bf16 head 13 % of its time
+// (81 -> 92 us at 131072 rows) before the launcher chose between two kernels instead of the kernel between two paths.
+template <typename WT, int NTL, int KIND, bool ROWS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(head_rb<WT, NTL, KIND>()))) void head_k(const mvae_head_args a) {
     constexpr int KG = op<WT>::KG, FE = op<WT>::FRAG_ELEMS;
     typedef typename op<WT>::frag frag;
@@ -131,6 +134,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(head_rb<WT,
                 loss_acc += rw * ce;
                 hit_acc += (counted && am == tfirst) ? 1.0f : 0.0f;
                 if (a.argmax) a.argmax[row] = (uint8_t)am;
+                if constexpr (ROWS) {                                     // the row's two addends, kept (per-window losses)
+                    a.row_out[(size_t)row * 2] = rw * ce;
+                    a.row_out[(size_t)row * 2 + 1] = (counted && am == tfirst) ? 1.0f : 0.0f;
+                }
             }
             if (rv) {
 #pragma unroll
@@ -153,6 +160,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(head_rb<WT,
                 loss_acc += rw * (pr - y) * (pr - y);
                 const float rounded = rintf(pr);                          // Keras binary_accuracy: round half to even
                 hit_acc += (counted && rounded == y) ? 1.0f : 0.0f;
+                if constexpr (ROWS) {
+                    a.row_out[(size_t)row * 2] = rw * (pr - y) * (pr - y);
+                    a.row_out[(size_t)row * 2 + 1] = (counted && rounded == y) ? 1.0f : 0.0f;
+                }
                 if (a.probs) a.probs[row] = pr;
                 if (a.argmax) a.argmax[row] = (uint8_t)rounded;
                 if (a.want_grad) st<WT>::store(dl + (size_t)row * NP, a.grad_scale * rw * 2.0f * (pr - y) * pr * (1.0f - pr));
@@ -235,7 +246,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(head_rb<WT,
     }
 }
 
-template <typename WT, int KIND>
+template <typename WT, int KIND, bool ROWS>
 int launch(const mvae_head_args& a, hipStream_t s) {
     const int ntl = (a.N + 15) / 16;
     const dim3 block(256);
@@ -245,20 +256,20 @@ int launch(const mvae_head_args& a, hipStream_t s) {
         return dim3(need < cap ? need : cap);
     };
     switch (ntl) {
-        case 1: hipLaunchKernelGGL((head_k<WT, 1, KIND>), grid(head_rb<WT, 1, KIND>()), block, 0, s, a); break;
-        case 2: hipLaunchKernelGGL((head_k<WT, 2, KIND>), grid(head_rb<WT, 2, KIND>()), block, 0, s, a); break;
+        case 1: hipLaunchKernelGGL((head_k<WT, 1, KIND, ROWS>), grid(head_rb<WT, 1, KIND>()), block, 0, s, a); break;
+        case 2: hipLaunchKernelGGL((head_k<WT, 2, KIND, ROWS>), grid(head_rb<WT, 2, KIND>()), block, 0, s, a); break;
         case 3:
-        case 4: hipLaunchKernelGGL((head_k<WT, 4, KIND>), grid(head_rb<WT, 4, KIND>()), block, 0, s, a); break;
+        case 4: hipLaunchKernelGGL((head_k<WT, 4, KIND, ROWS>), grid(head_rb<WT, 4, KIND>()), block, 0, s, a); break;
         case 5: case 6: case 7:
-        case 8: hipLaunchKernelGGL((head_k<WT, 8, KIND>), grid(head_rb<WT, 8, KIND>()), block, 0, s, a); break;
+        case 8: hipLaunchKernelGGL((head_k<WT, 8, KIND, ROWS>), grid(head_rb<WT, 8, KIND>()), block, 0, s, a); break;
         default:
             // 9..12 tiles (softmax heads only; one-hot rows of the full MIDI range, plus the silent and the instrument-category
             // columns): one instantiation per tile count - d(logits) has NP columns that the dW GEMM reads again at T*B rows
             if constexpr (KIND == 0) {
-                if (ntl == 9) hipLaunchKernelGGL((head_k<WT, 9, KIND>), grid(1), block, 0, s, a);
-                else if (ntl == 10) hipLaunchKernelGGL((head_k<WT, 10, KIND>), grid(1), block, 0, s, a);
-                else if (ntl == 11) hipLaunchKernelGGL((head_k<WT, 11, KIND>), grid(1), block, 0, s, a);
-                else if (ntl == 12) hipLaunchKernelGGL((head_k<WT, 12, KIND>), grid(1), block, 0, s, a);
+                if (ntl == 9) hipLaunchKernelGGL((head_k<WT, 9, KIND, ROWS>), grid(1), block, 0, s, a);
+                else if (ntl == 10) hipLaunchKernelGGL((head_k<WT, 10, KIND, ROWS>), grid(1), block, 0, s, a);
+                else if (ntl == 11) hipLaunchKernelGGL((head_k<WT, 11, KIND, ROWS>), grid(1), block, 0, s, a);
+                else if (ntl == 12) hipLaunchKernelGGL((head_k<WT, 12, KIND, ROWS>), grid(1), block, 0, s, a);
                 else return MVAE_E_UNSUPPORTED;
                 break;
             }
@@ -266,6 +277,12 @@ int launch(const mvae_head_args& a, hipStream_t s) {
     }
     MVAE_CHECK_LAUNCH();
     return MVAE_OK;
+}
+
+// with row_out the kernels that keep the rows' addends, else the ones that do not know the field
+template <typename WT, int KIND>
+int launch(const mvae_head_args& a, hipStream_t s) {
+    return a.row_out ? launch<WT, KIND, true>(a, s) : launch<WT, KIND, false>(a, s);
 }
 
 }  // namespace

@@ -132,9 +132,19 @@ __global__ __launch_bounds__(LT) void latent_chain_fwd_k(const mvae_latent_chain
                 zh[w * pad4(zin) + j] = v;
             }
             kl = wave_sum(kl);
+            const bool styled = a.style_target && a.C > 0;
+            if (l == 0 && b >= a.B_valid) {      // padding rows add nothing: their per-row outputs say so
+                if (a.kl_rows) a.kl_rows[b] = 0.0f;
+                if (a.style_rows && styled) {
+                    a.style_rows[(size_t)b * 2] = 0.0f;
+                    a.style_rows[(size_t)b * 2 + 1] = 0.0f;
+                }
+            }
             if (l == 0 && b < a.B_valid) {
-                atomicAdd(a.scalars, a.inv_batch * a.beta * (-0.5f) * kl);
-                if (a.style_target && a.C > 0) {
+                const float klb = a.inv_batch * a.beta * (-0.5f) * kl;
+                atomicAdd(a.scalars, klb);
+                if (a.kl_rows) a.kl_rows[b] = klb;
+                if (styled) {
                     const int C = a.C;
                     const float* zr = zh + w * pad4(zin);
                     float mx = -INFINITY;
@@ -152,8 +162,13 @@ __global__ __launch_bounds__(LT) void latent_chain_fwd_k(const mvae_latent_chain
                     }
                     const float rw = a.style_row_weight ? a.style_row_weight[b] : a.inv_batch;
                     const float ce = tg < C ? -logf(fminf(fmaxf(pt, CE_EPS), 1.0f - CE_EPS)) : 0.0f;
+                    const float hit = am == (tg < C ? tg : 0) ? 1.0f : 0.0f;
                     atomicAdd(a.scalars + 1, rw * ce);
-                    atomicAdd(a.scalars + 2, am == (tg < C ? tg : 0) ? 1.0f : 0.0f);
+                    atomicAdd(a.scalars + 2, hit);
+                    if (a.style_rows) {
+                        a.style_rows[(size_t)b * 2] = rw * ce;
+                        a.style_rows[(size_t)b * 2 + 1] = hit;
+                    }
                 }
             }
         }

@@ -25,7 +25,9 @@ __global__ __launch_bounds__(256) void latent_fwd_k(const mvae_latent_fwd_args a
     }
     kl = wave_sum(kl);
     if (l == 0) {
-        atomicAdd(a.scalars, a.inv_batch * a.beta * (-0.5f) * kl);
+        const float klb = a.inv_batch * a.beta * (-0.5f) * kl;
+        atomicAdd(a.scalars, klb);
+        if (a.kl_rows) a.kl_rows[b] = klb;
         if (a.style_target && a.C > 0) {
             const int C = a.C;
             float mx = -INFINITY;
@@ -50,8 +52,13 @@ __global__ __launch_bounds__(256) void latent_fwd_k(const mvae_latent_fwd_args a
             }
             const float rw = a.style_row_weight ? a.style_row_weight[b] : a.inv_batch;
             const float ce = tg < C ? -logf(fminf(fmaxf(pt, CE_EPS), 1.0f - CE_EPS)) : 0.0f;
+            const float hit = am == (tg < C ? tg : 0) ? 1.0f : 0.0f;
             atomicAdd(a.scalars + 1, rw * ce);
-            atomicAdd(a.scalars + 2, am == (tg < C ? tg : 0) ? 1.0f : 0.0f);
+            atomicAdd(a.scalars + 2, hit);
+            if (a.style_rows) {
+                a.style_rows[(size_t)b * 2] = rw * ce;
+                a.style_rows[(size_t)b * 2 + 1] = hit;
+            }
         }
     }
 }

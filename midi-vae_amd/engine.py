@@ -130,6 +130,7 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
         self._grad_streams = None        # (s_grad, s_grad2) unless overridden for a phase
         self._n_side = 0                 # recurrences running beside the stack being scheduled (residency, _pipelined)
         self._cur_B = self.maxB          # padded batch of the call being scheduled
+        self._pw = False                 # a per-window evaluation step in progress (eval_step(per_window=True))
         self._sample_mode, self._want_vel = None, False      # a 'choice' decode in progress (Engine.decode): (heads with supplied uniforms, tries)
         self.num_cus = torch.cuda.get_device_properties(self.device).multi_processor_count
         self._occ = {k: max(1, hl.load().mvae_occupancy(i)) for i, k in enumerate(("dx", "proj", "kstream"))}
@@ -728,7 +729,7 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
             pack=self._v("pack", B, H) if self.has_pack else None, extra=self._v("extra", B, H) if s.extra_layer else None,
             mu=self._v("mu", B, Z), logvar=self._v("lv", B, Z), zh=self._v("zh", B, s.zin),
             style_probs=self._v("style_p", B, s.C) if s.style else None, scalars=self.scal[S_KL:S_KL + 3],
-            S=self._v("S", B, self.n_init * H) if with_init else None)
+            S=self._v("S", B, self.n_init * H) if with_init else None, **self._pw_latent(B))
         if ok:
             self._tail = (self._v("extra", B, H) if s.extra_layer else self._v("pack", B, H) if self.has_pack
                           else self._v("cat", B, H))
@@ -845,7 +846,9 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
         ops.head(h.kind, self.kind, R, H, h.N, top, self._v(n + ".wt", h.NP, H), P[h.out + ".b"], grad_scale=h.weight,
                  probs=self._v("out.%s_p" % n, R, h.N) if want_probs else None, argmax=self._v(n + ".argmax", R),
                  dlogits=self._v(n + ".dl", R, h.NP) if (self.training and tg) else None, **self._fused_head_bwd(n, tg),
-                 scalars=self.scal[h.slot:h.slot + 2], b_stride=B, b_valid=ops.ParamInt(Breal, ops.PARAM_B), **tgt)
+                 scalars=self.scal[h.slot:h.slot + 2], b_stride=B, b_valid=ops.ParamInt(Breal, ops.PARAM_B),
+                 row_out=self._pw_rows(n, h.T, B), **tgt)
+        self._pw_reduce(n, h.T, B)
 
     def _head_sample(self, h, top, B, Breal, r0, r1):
         """rows [r0, r1) of a softmax decoder head's 'choice' decode (mvae_head_sample): seed, first window, temperature, cutoff
@@ -1309,9 +1312,25 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
         return self._stager
 
 
-    def eval_step(self, B, want_probs=False):
-        """Forward + losses only (``autoencoder.evaluate`` / ``autoencoder.predict``)."""
-        self._planned(("eval", B, float(self.norm_B), bool(want_probs)), lambda: self._eval_step(B, want_probs), params=self._call_params(B))
+    def eval_step(self, B, want_probs=False, per_window=False):
+        """Forward + losses only (``autoencoder.evaluate`` / ``autoencoder.predict``).
+        ``per_window``: every head and the latent kernels also keep each row's addends (mvae_head_args.row_out, kl_rows,
+        style_rows), the engine sums them over time per window, and window_metrics(B) reads them back as one block.  The row
+        weights staged for such a step are those of a ONE-window batch (Stager.stage with ``Norm.one_window``), so a window's sums
+        are its own Keras losses; the batch scalars of such a step are then sums over the windows, not means."""
+        per_window = bool(per_window)
+        if per_window:
+            if self.spec.signature:
+                raise NotImplementedError("per-window evaluation does not cover the signature head (signature_decoder=True): its "
+                                          "kernel has no per-row output; evaluate the songs one by one with evaluate()")
+            self._pw_alloc()        # (at the first use, and outside the recording: the allocation is a torch fill)
+        self._pw = per_window
+        try:
+            # per_window is part of the key: a recorded evaluate never replays as a per-window step, nor the reverse
+            self._planned(("eval", B, float(self.norm_B), bool(want_probs), per_window), lambda: self._eval_step(B, want_probs),
+                          params=self._call_params(B))
+        finally:
+            self._pw = False
 
     def _eval_step(self, B, want_probs):
         self._have_targets = True

@@ -282,3 +282,49 @@ class Buffers(object):
             st[name] = self._in_block[o:o + nbytes].view(tdt)
         self._stager = None
 
+
+    # ------------------------------------------------------------------------------------------------------
+    # per-window evaluation (eval_step(per_window=True)): the rows' addends and their sums over time
+    # ------------------------------------------------------------------------------------------------------
+    def _pw_pairs(self):
+        """the (loss, hits) pairs of the per-window block, in block order: every head that runs through mvae_head - the decoder's
+        heads, the classifiers on its outputs - then the style head; the KL column follows the pairs"""
+        return [h.name for h in self.heads] + (["style"] if self.spec.style else [])
+
+    def _pw_alloc(self):
+        """Allocated at the first per-window step, not with the engine: ``pw.<head>`` (T_head, B, 2) f32, the addends of every row
+        of a head (2048 windows x T = 4096: 67 MB per head), and ``pw.block``, per window a (loss, hits) pair for every entry
+        of _pw_pairs and the KL term - what window_metrics reads."""
+        if "pw.block" in self.store:
+            return
+        f32 = dict(dtype=torch.float32, device=self.device)
+        for h in self.heads:
+            if h.T > 1:         # (a head of one step per window writes its pair of the block itself)
+                self.store["pw." + h.name] = torch.zeros(h.T * self.maxB * 2, **f32)
+        self.store["pw.block"] = torch.zeros((2 * len(self._pw_pairs()) + 1) * self.maxB, **f32)
+
+    def _pw_pair(self, name, B):
+        """the (B, 2) pair of ``name`` inside the block of a B-row (padded) step"""
+        i = self._pw_pairs().index(name)
+        return self.store["pw.block"][2 * B * i:2 * B * (i + 1)].view(B, 2)
+
+    def _pw_rows(self, name, T, B):
+        """``row_out`` of head ``name`` in a per-window step (None otherwise)"""
+        if not self._pw:
+            return None
+        return self._pw_pair(name, B) if T == 1 else self._v("pw." + name, T * B, 2)
+
+    def _pw_reduce(self, name, T, B):
+        """the head's rows summed over time into its pair of the block, behind the head on its stream"""
+        if self._pw and T > 1:
+            ops.sum_over_time(self._v("pw." + name, T * B * 2), T, 2 * B, self._pw_pair(name, B).view(-1))
+
+    def _pw_latent(self, B):
+        """``kl_rows`` / ``style_rows`` of the latent launch of a per-window step (nothing otherwise)"""
+        if not self._pw:
+            return {}
+        n = len(self._pw_pairs())
+        out = dict(kl_rows=self.store["pw.block"][2 * B * n:2 * B * n + B])
+        if self.spec.style:
+            out["style_rows"] = self._pw_pair("style", B)
+        return out

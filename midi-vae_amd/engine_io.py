@@ -196,6 +196,21 @@ class Results(object):
             B = self.norm_B             # a shard of a global minibatch: this rank's SHARE of the global means
         return self._metrics_from(v, B)
 
+    def window_metrics(self, B):
+        """(B, N_SCALARS) float64: the scalar slots of every window of the last ``eval_step(B, per_window=True)`` - row b is what
+        ``scal`` would hold had window b been evaluated alone, so ``_metrics_from(row, 1)`` is that window's metric dict.  ONE
+        device->host read for the whole batch."""
+        Bp, pairs = self.pad16(B), self._pw_pairs()
+        blk = self.store["pw.block"][:(2 * len(pairs) + 1) * Bp].cpu().numpy().astype(np.float64)
+        self.check_pipeline()
+        out = np.zeros((B, N_SCALARS))
+        slot = {h.name: h.slot for h in self.heads}
+        slot["style"] = S_STYLE_LOSS
+        for i, name in enumerate(pairs):
+            out[:, slot[name]:slot[name] + 2] = blk[2 * Bp * i:2 * Bp * (i + 1)].reshape(Bp, 2)[:B]
+        out[:, S_KL] = blk[2 * Bp * len(pairs):][:B]
+        return out
+
     def _metrics_from(self, v, B):
         """metric dict from the scalar slots: loss slots hold batch means already, hit slots counts over ``B`` windows"""
         s = self.spec

@@ -87,7 +87,7 @@ class OptionalGraph(object):
                  target_idx=self._v("in.c_idx", B) if tg else None, row_weight=self._v("in.rw_" + a.key, B) if tg else None,
                  grad_scale=a.weight, probs=self._v("out.%s_p" % a.key, B, s.C) if want_probs else None,
                  argmax=self._v(a.key + ".argmax", B), dlogits=self._v(a.key + ".dl", B, h.NP) if (self.training and tg) else None,
-                 scalars=self.scal[a.slot:a.slot + 2], b_stride=B, b_valid=Breal)
+                 scalars=self.scal[a.slot:a.slot + 2], b_stride=B, b_valid=Breal, row_out=self._pw_rows(a.key, 1, B))
 
     def _aux_backward(self, a, B):
         """... and back: Dense, BPTT, the classifier's parameters, then its gradient w.r.t. the source head's PROBABILITIES folded
@@ -135,7 +135,7 @@ class OptionalGraph(object):
                        self._v("in.eps", B, Z), zh, self.scal[S_KL:S_KL + 3],
                        style_target=self._v("in.c_idx", Breal) if (s.style and self._have_targets) else None,
                        style_row_weight=self._v("in.rw_style", Breal) if (s.style and self._have_targets) else None,
-                       style_probs=self._v("style_p", B, s.C) if s.style else None, ldz=s.zin)
+                       style_probs=self._v("style_p", B, s.C) if s.style else None, ldz=s.zin, **self._pw_latent(B))
 
     def _latent_backward_unfused(self, Breal, B):
         """initial-state Denses, latent block and encoder tail Denses backward, one launch per operation; returns d(cat)"""

@@ -77,7 +77,8 @@ class HeadArgs(C.Structure):
     _fields_ = [("kind", _i32), ("dtype", _i32), ("R", _i32), ("H", _i32), ("N", _i32), ("want_grad", _i32),
                 ("hs", _vp), ("wt", _vp), ("bias", _vp), ("target_idx", _vp), ("target_val", _vp),
                 ("row_weight", _vp), ("grad_scale", _f32), ("probs", _vp), ("argmax", _vp), ("dlogits", _vp),
-                ("scalars", _vp), ("b_stride", _i32), ("b_valid", _i32), ("wc", _vp), ("dhs", _vp), ("target_idx2", _vp)]
+                ("scalars", _vp), ("b_stride", _i32), ("b_valid", _i32), ("wc", _vp), ("dhs", _vp), ("target_idx2", _vp),
+                ("row_out", _vp)]
 
 
 class SampleCtl(C.Structure):
@@ -98,7 +99,8 @@ SAMPLE_MAX_TRIES = 4
 class LatentFwdArgs(C.Structure):
     _fields_ = [("B", _i32), ("Z", _i32), ("C", _i32), ("beta", _f32), ("prior_mean", _f32), ("prior_std", _f32),
                 ("inv_batch", _f32), ("mu", _vp), ("logvar", _vp), ("eps", _vp), ("style_target", _vp),
-                ("style_row_weight", _vp), ("z", _vp), ("style_probs", _vp), ("scalars", _vp), ("ldz", _i32)]
+                ("style_row_weight", _vp), ("z", _vp), ("style_probs", _vp), ("scalars", _vp), ("ldz", _i32),
+                ("kl_rows", _vp), ("style_rows", _vp)]
 
 
 class LatentBwdArgs(C.Structure):
@@ -113,7 +115,7 @@ class LatentChainFwdArgs(C.Structure):
                 [(n, _f32) for n in ("beta", "prior_mean", "prior_std", "inv_batch")] +
                 [(n, _vp) for n in ("cat", "w_pack", "b_pack", "w_extra", "b_extra", "w_mu", "b_mu", "w_lv", "b_lv", "w_init",
                                     "b_init", "eps", "style_target", "style_row_weight", "pack", "extra", "mu", "logvar", "zh",
-                                    "style_probs", "scalars", "S")])
+                                    "style_probs", "scalars", "S", "kl_rows", "style_rows")])
 
 
 class LatentChainBwdArgs(C.Structure):

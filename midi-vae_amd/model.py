@@ -50,6 +50,19 @@ class History(object):
         return self._history
 
 
+def song_means(rows, lengths):
+    """(n_songs, k): the mean of every column of ``rows`` (n, k) over each song's windows; ``lengths`` are the songs' window
+    counts, in order, and sum to n.  Pure NumPy (Autoencoder.evaluate_songs reduces its per-window block with it)."""
+    rows = np.asarray(rows, np.float64)
+    lengths = [int(v) for v in lengths]
+    if any(v <= 0 for v in lengths):
+        raise ValueError("every song needs at least one window")
+    if sum(lengths) != rows.shape[0]:
+        raise ValueError("the song lengths sum to %d, the window array has %d rows" % (sum(lengths), rows.shape[0]))
+    starts = np.concatenate([[0], np.cumsum(lengths)[:-1]]).astype(np.int64)
+    return np.add.reduceat(rows, starts, axis=0) / np.asarray(lengths, np.float64)[:, None]
+
+
 class DeviceLatent(object):
     """Sampled z of every window of a song, resident in HBM - what ``encoder.predict(..., device=True)`` returns instead of a
     host array.  Passed in the history slot of the fit / evaluate input list it stands for the ROLLED history of reference
@@ -851,6 +864,87 @@ class Autoencoder(_ModelView):
         losses = [src for k, src in pairs if "loss" in k]
         accs = [src for k, src in pairs if "acc" in k]
         return [m[k] for k in losses + accs]
+
+    def _metric_columns(self):
+        """engine metric names in the order of ``metrics_names``: the losses, then the accuracies"""
+        pairs = self._history_keys()
+        return [src for k, src in pairs if "loss" in k] + [src for k, src in pairs if "acc" in k]
+
+    def _window_rows(self, x, y, eps):
+        """(n, len(metrics_names)) float64: every window's metrics from per-window passes of the forward-only engine at its own
+        batch; ``eps`` (n, Z) are the draws, already in the order the caller's loop would have taken them"""
+        from .staging import Norm
+        sp = self._s.spec
+        a = self._unpack_x(x)
+        a.update(self._unpack_y(y))
+        n = np.asarray(a["X"]).shape[0]
+        a["hist_dev"] = None
+        cols = self._metric_columns()
+        out = np.zeros((n, len(cols)))
+        if n == 0:
+            return out
+        eng = self._s.get_infer(n)
+        st = eng.stager()
+        norm = Norm.one_window(sp.T)
+        for lo in range(0, n, eng.maxB):
+            hi = min(n, lo + eng.maxB)
+            B = st.stage(lo, hi, eps=eps[lo:hi], norm=norm, **a)
+            eng.eval_step(B, per_window=True)
+            m = eng._metrics_from(eng.window_metrics(B).T, 1)        # (slot vectors over the windows: the dict holds (B,) arrays)
+            for j, k in enumerate(cols):
+                out[lo:hi, j] = m[k]
+        return out
+
+    def _check_per_window(self, xs):
+        sp = self._s.spec
+        if sp.signature:
+            raise NotImplementedError("per-window evaluation does not cover the signature head (signature_decoder=True); "
+                                      "call evaluate() song by song")
+        for x in xs:
+            if isinstance(self._unpack_x(x).get("hist"), DeviceLatent):
+                raise TypeError("evaluate_windows / evaluate_songs take the history as a host array (n, latent_dim) per song - "
+                                "pass DeviceLatent.numpy(), or encoder.predict(...) without device=True")
+
+    def evaluate_windows(self, x, y, batch_size=32):
+        """Per-window ``evaluate``: an (n, len(metrics_names)) float64 array whose row i is what ``evaluate`` returns for window i
+        alone - loss columns the window's Keras losses (the total included), accuracy columns its hit fractions.  All windows run
+        through the forward-only engine at its own batch; the losses are summed per window on the device and read back as one
+        block per pass.  Epsilon is drawn per ``batch_size`` windows, as ``evaluate(x, y, batch_size)`` draws it.  Under data
+        parallelism every rank evaluates everything."""
+        self._check_per_window([x])
+        n = np.asarray(_as_list(x)[0]).shape[0]
+        return self._window_rows(x, y, self._s.epsilon_batches(n, batch_size))
+
+    def evaluate_songs(self, xs, ys, batch_size=32):
+        """``[evaluate(x, y, batch_size) for x, y in zip(xs, ys)]`` as ONE chip-filling pass over the windows of all songs
+        (reference vae_training.py:243-351 evaluates song by song: 20-200 windows and one metric read each).  ``xs`` / ``ys``: lists
+        of per-song input / output lists as ``evaluate`` takes them, the history a host array built per song.  Returns one metric
+        list per song, aligned with ``metrics_names``: the mean over the song's windows - what Keras' batch-size-weighted mean of
+        batch means is without sample weights.  The epsilon stream is consumed as the loop would consume it: song by song, per
+        ``batch_size`` windows within a song."""
+        xs, ys = list(xs), list(ys)
+        if len(xs) != len(ys):
+            raise ValueError("evaluate_songs: %d input lists for %d output lists - pass one x and one y per song" % (len(xs), len(ys)))
+        if not xs:
+            return []
+        self._check_per_window(xs)
+        xs, ys = [_as_list(x) for x in xs], [_as_list(y) for y in ys]
+        lengths = [np.asarray(x[0]).shape[0] for x in xs]
+        for i, n in enumerate(lengths):
+            if n <= 0:
+                raise ValueError("evaluate_songs: song %d has no windows - leave empty songs out of the lists" % i)
+        if len({len(x) for x in xs}) != 1 or len({len(y) for y in ys}) != 1:
+            raise ValueError("evaluate_songs: every song must pass the same inputs and outputs, in the same order")
+        eps = np.concatenate([self._s.epsilon_batches(n, batch_size) for n in lengths], 0)
+        # one array per list entry over all songs.  The wide one-hot tensors (notes in, notes out, next notes: 31 KB of float64 per
+        # window at T = 64) are converted to one byte per row song by song first - the pass over them staging makes anyway, through
+        # the same host packer and with its refusal of rows that are not one-hot - so that what is joined is 1/488 of them
+        from .staging import host_onehot_to_index
+        wide = (lambda a: np.ndim(a) == 3 and np.shape(a)[2] > 2) if not self._s.spec.attach else (lambda a: False)
+        join = lambda parts: np.concatenate([host_onehot_to_index(a) if wide(a) else np.asarray(a) for a in parts], 0)
+        x = [join([xi[k] for xi in xs]) for k in range(len(xs[0]))]
+        y = [join([yi[k] for yi in ys]) for k in range(len(ys[0]))]
+        return [list(r) for r in song_means(self._window_rows(x, y, eps), lengths)]
 
     def predict(self, x, batch_size=32, verbose=0):
         sp = self._s.spec

@@ -286,10 +286,12 @@ def head_np(N):
 
 
 def head(kind, dtype, R, H, N, hs, wt, bias, *, target_idx=None, target_val=None, row_weight=None, grad_scale=1.0,
-         probs=None, argmax=None, dlogits=None, scalars=None, b_stride=0, b_valid=0, wc=None, dhs=None, target_idx2=None):
+         probs=None, argmax=None, dlogits=None, scalars=None, b_stride=0, b_valid=0, wc=None, dhs=None, target_idx2=None,
+         row_out=None):
+    """``row_out`` (R, 2) f32 or a view of a larger one that starts at this launch's first row: every row's loss and hit addend"""
     a = hl.HeadArgs(kind, dtype, R, H, N, int(dlogits is not None), hs.data_ptr(), _p(wt), _p(bias), _p(target_idx),
                     _p(target_val), _p(row_weight), float(grad_scale), _p(probs), _p(argmax), _p(dlogits), _p(scalars),
-                    b_stride, b_valid, _p(wc), _p(dhs), _p(target_idx2))
+                    b_stride, b_valid, _p(wc), _p(dhs), _p(target_idx2), _pv(row_out))
     _tag(a, "b_valid", b_valid)
     _note_fields(0, [a])
     hl.check(hl.load().mvae_head(a, _stream()), "mvae_head")
@@ -310,9 +312,9 @@ def head_sample(dtype, R, H, N, hs, wt, bias, out, *, uniforms=None, u_stride=0,
 
 
 def latent_fwd(B, Z, C, beta, prior_mean, prior_std, inv_batch, mu, logvar, eps, z, scalars, *, style_target=None,
-               style_row_weight=None, style_probs=None, ldz=0):
+               style_row_weight=None, style_probs=None, ldz=0, kl_rows=None, style_rows=None):
     a = hl.LatentFwdArgs(B, Z, C, beta, prior_mean, prior_std, inv_batch, _p(mu), _p(logvar), _p(eps),
-                         _p(style_target), _p(style_row_weight), _pv(z), _p(style_probs), _p(scalars), ldz)
+                         _p(style_target), _p(style_row_weight), _pv(z), _p(style_probs), _p(scalars), ldz, _p(kl_rows), _p(style_rows))
     hl.check(hl.load().mvae_latent_fwd(a, _stream()), "mvae_latent_fwd")
 
 

@@ -42,6 +42,13 @@ class Norm(object):
         self.nz_cinstr = int(B) if nz_cinstr is None else nz_cinstr
 
     @staticmethod
+    def one_window(T):
+        """the normalisers of a batch of ONE window with unit weights, whatever number of windows is staged with them: every row
+        weight is 1 / (steps of its head), 1 / batch is 1 - the sums over a window's rows are then the Keras losses of that window
+        evaluated alone (per-window evaluation, Engine.eval_step(per_window=True))"""
+        return Norm(1, T, 1, 1, 1)
+
+    @staticmethod
     def of(lo, hi, T, w_notes=None, w_instr=None, w_vel=None, w_style=None, w_held=None, w_next=None, w_sig=None, w_cnotes=None,
            w_cinstr=None):
         B = hi - lo

@@ -69,14 +69,31 @@ def history_for(model, song, s, use_encoder, on_device=True):
     return H
 
 
-def run_epoch(model, songs, s, epoch, train):
+def run_epoch(model, songs, s, epoch, train, batched=False):
+    """``batched`` (test pass only): every song's windows in ONE chip-filling pass (autoencoder.evaluate_songs) instead of one
+    under-filled evaluate call and one metric read per song.  The histories are then host arrays built song by song first, so the
+    model's epsilon stream is drawn in another order than in the per-song loop (all history draws, then all evaluate draws)."""
     names = model.autoencoder.metrics_names
     enum, seen, total = [], {}, {n: names.count(n) for n in names}
     for n in names:                                            # reference vae_training.py:172-187
         seen[n] = seen.get(n, 0) + 1
         enum.append("%s_%d" % (n, seen[n]) if total[n] > 1 else n)
     agg, pending = {}, []
-    for song in songs:
+    if batched and not train:
+        xs, ys = [], []
+        for song in songs:
+            H = history_for(model, song, s, use_encoder=True, on_device=False)
+            x, y = vae_definition.prepare_autoencoder_input_and_output_list(
+                song["X"], song["Y"], song["C"], song["I"], song["V"], song["D"], song["S"], H)
+            xs.append(x)
+            ys.append(y)
+        for vals in model.autoencoder.evaluate_songs(xs, ys, batch_size=s["batch_size"]):
+            for k, v in zip(enum, vals):
+                agg[k] = agg.get(k, 0.0) + v
+        songs_left = []
+    else:
+        songs_left = songs
+    for song in songs_left:
         H = history_for(model, song, s, use_encoder=(epoch > 0 or not train))
         if train:
             x, y, w = vae_definition.prepare_autoencoder_input_and_output_list(
@@ -118,6 +135,8 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend when WORLD_SIZE > 1")
     ap.add_argument("--pickle-dir", default="", help="a dataset cache written by the reference (import_midi.py:548-571: V_train.pickle ... "
                     "test_paths.pickle) instead of synthetic songs")
+    ap.add_argument("--batched-test", action="store_true", help="run the test pass of all songs as one chip-filling per-window "
+                    "pass (autoencoder.evaluate_songs) instead of one evaluate call per song")
     args = ap.parse_args()
     s = vars(settings)
 
@@ -164,7 +183,7 @@ def main():
         if e % s["test_step"] == 0:
             # EVERY rank: encoder.predict and evaluate shard each song over the ranks (and draw from the same generator on every
             # rank, so the epsilon streams of the replicas stay identical) - reference vae_training.py:286-300 on all GPUs
-            te = run_epoch(model, test, s, e, train=False)
+            te = run_epoch(model, test, s, e, train=False, batched=args.batched_test)
             if rank == 0:
                 print("         test  loss %.4f notes %.4f acc %.4f kl %.5f" % (
                     te["loss"], te.get("decoder_loss_1", te["loss"]), te.get("decoder_acc_1", 0.0), te["kl_loss"]))
