@@ -126,6 +126,20 @@ class LatentChainBwdArgs(C.Structure):
                                     "d_extra", "d_pack", "dcat")])
 
 
+class DescArgs(C.Structure):
+    """mvae_desc_args of include/midivae_descriptors.h"""
+    _fields_ = [("idx", _vp), ("stride_t", _i64), ("stride_w", _i64), ("n", _i32), ("T", _i32), ("voices", _i32), ("silent", _i32),
+                ("n_pitch", _i32), ("low_crop", _i32), ("resolution", _i32), ("ld_sig", _i32), ("tonal", _vp), ("sig_out", _vp),
+                ("harm_out", _vp)]
+
+
+DESC_ABI_VERSION = 1
+# the second header, include/midivae_descriptors.h (versioned on its own: SIGNATURES and ABI_VERSION do not move with it)
+DESC_SIGNATURES = {
+    "mvae_desc_abi_version": (_i32, []),
+    "mvae_desc_windows": (_i32, [C.POINTER(DescArgs), _vp]),
+}
+
 # name -> (restype, argtypes); every symbol include/midivae_hip.h declares
 SIGNATURES = {
     "mvae_abi_version": (_i32, []),
@@ -211,13 +225,16 @@ def load():
             "%s not found - build it with `make -C midi-vae_amd/csrc` (or __graft_entry__.build()); "
             "the MIDI-VAE engine has no CPU fallback" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(DESC_SIGNATURES.items()):
         fn = getattr(lib, name)      # AttributeError here = ABI drift between header and library
         fn.restype = res
         fn.argtypes = args
     if lib.mvae_abi_version() != ABI_VERSION:
         raise HipLibraryMissing("ABI version mismatch: library %d, binding %d - rebuild with `make -C midi-vae_amd/csrc`"
                                 % (lib.mvae_abi_version(), ABI_VERSION))
+    if lib.mvae_desc_abi_version() != DESC_ABI_VERSION:
+        raise HipLibraryMissing("descriptor ABI version mismatch: library %d, binding %d - rebuild with `make -C midi-vae_amd/csrc`"
+                                % (lib.mvae_desc_abi_version(), DESC_ABI_VERSION))
     _lib = lib
     return lib
 

@@ -479,12 +479,13 @@ class Decoder(_ModelView):
                 i += 1
         return res
 
-    def _run(self, x, batch_size, want_probs=True, sample=None, all_heads=False):
+    def _run(self, x, batch_size, want_probs=True, sample=None, all_heads=False, describe=None):
         """decoder forward over all windows at the forward-only engine's batch (``batch_size`` is the caller's: results are per
         window); every rank decodes everything it is given - decoding is pure replicas.
         ``sample``: the resolved arguments of a 'choice' decode (_sample_spec) - every engine batch is told the caller's index of
         its first window, so a window's draws do not depend on the batches.  ``all_heads``: the third result is a dict head ->
-        indices of every softmax head (+ 'velocity')."""
+        indices of every softmax head (+ 'velocity').  ``describe``: descriptors.params(...) - the second result is a list of
+        descriptors.decoded_batch dicts, one per engine batch, instead of the concatenated note indices."""
         sp = self._s.spec
         a = self._unpack(x)
         z = np.asarray(a.pop("z"))
@@ -504,6 +505,11 @@ class Decoder(_ModelView):
                 eng.decode(B, want_probs=want_probs, sample=spec, want_velocity=all_heads and sp.meta_velocity)
             if want_probs:
                 outs.append(eng.outputs(B))
+            if describe is not None:       # behind the decode on this stream, outside the step plans; one read per engine batch
+                from . import descriptors
+                rows = eng._v("notes.argmax" if sample is None else "notes.choice", sp.T, eng.pad16(B))
+                idxs.append(descriptors.decoded_batch(rows, B, describe))
+                continue
             if sample is None:
                 idxs.append(eng.note_indices(B))
                 if all_heads:
@@ -514,6 +520,8 @@ class Decoder(_ModelView):
             if all_heads and sp.meta_velocity:
                 heads[-1]["velocity"] = eng.velocity(B)
         eng.check_pipeline()
+        if describe is not None:
+            return outs, idxs
         notes = np.concatenate(idxs, 0) if idxs else np.zeros((0, sp.T), np.uint8)
         if not all_heads:
             return outs, notes
@@ -583,6 +591,29 @@ class Decoder(_ModelView):
         n = np.asarray(self._unpack(x)["z"]).shape[0]
         sample = self._sample_spec(n, sample_method, temperature, seed, uniforms, self._softmax_heads())
         return self._run(x, batch_size, want_probs=False, sample=sample)[1]
+
+    def predict_descriptors(self, x, batch_size=32, sample_method="argmax", temperature=None, seed=None, uniforms=None):
+        """predict_note_indices plus the window descriptors of what was decoded: dict ``notes`` (n, T) uint8, ``signature`` (n, 15)
+        and ``harmonicity`` (n, max_voices, max_voices) float64 (midi_vae_amd.descriptors; reference data_class.py:25-215).  The
+        descriptors are computed on the device from the decode's own time-major index buffer, enqueued behind the decode; one
+        device-to-host read per engine batch brings all three.  Pitch range, silent column and segment length come from
+        ``decoder.sample_settings`` (None: the defaults of config.build_settings()); arguments as predict_note_indices."""
+        from . import descriptors
+        s = self.sample_settings
+        if s is None:
+            from .config import build_settings
+            s = build_settings()
+        p, sp = descriptors.params(s), self._s.spec
+        if p["voices"] != sp.V:
+            raise ValueError("max_voices of the settings (%d) is not the model's (%d)" % (p["voices"], sp.V))
+        descriptors._check(sp.T, p, True)
+        n = np.asarray(self._unpack(x)["z"]).shape[0]
+        sample = self._sample_spec(n, sample_method, temperature, seed, uniforms, self._softmax_heads())
+        parts = self._run(x, batch_size, want_probs=False, sample=sample, describe=p)[1]
+        if not parts:
+            return dict(notes=np.zeros((0, sp.T), np.uint8), signature=np.zeros((0, descriptors.SIGNATURE_LENGTH)),
+                        harmonicity=np.zeros((0, sp.V, sp.V)))
+        return {k: np.concatenate([d[k] for d in parts], 0) for k in ("notes", "signature", "harmonicity")}
 
     def predict_indices(self, x, batch_size=32, sample_method="argmax", temperature=None, seed=None, uniforms=None):
         """The decoded index of EVERY softmax head - dict 'notes' (n, T), 'instr' (n, max_voices), 'held' (n, T), 'next' (n, T)

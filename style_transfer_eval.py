@@ -16,6 +16,8 @@ import numpy as np
 
 import settings
 import vae_definition
+import data_class
+from midi_vae_amd import descriptors
 from midi_vae_amd.classifier import StyleClassifier
 from midi_vae_amd.config import create_kwargs
 from style_classifier_training import synthetic_songs
@@ -47,8 +49,14 @@ def main():
             hs.append(model.autoencoder.fit(x, y, epochs=1, batch_size=bs, shuffle=False, sample_weight=w, verbose=False))
             clf.fit(sg["X"], np.tile(np.eye(nc)[sg["C"]][None], (sg["X"].shape[0], 1)), epochs=1, batch_size=bs, shuffle=False)
         print("epoch %d: VAE loss %.4f" % (e, np.mean([h.history["loss"][0] for h in hs])))
+    # the training signatures of every class: what a switched decode is measured against (vae_evaluation.py:1542-1628, :2836-2862)
+    class_stats = {}
+    for c in sorted({sg["C"] for sg in songs}):
+        sigs = np.concatenate([descriptors.signature_vectors(sg["X"], s) for sg in songs if sg["C"] == c], 0)
+        class_stats[c] = data_class.get_mean_and_cov_from_vector_list(sigs)
     t0 = time.time()
     n_win = kept = switched = 0
+    harm, distances = {"kept": [], "switched": []}, []
     for sg in songs:
         X, I, V, D, C = sg["X"], sg["I"], sg["V"], sg["D"], sg["C"]
         n = X.shape[0]
@@ -58,7 +66,11 @@ def main():
         z2[:, C], z2[:, target] = z[:, target], z[:, C]                                                     # :2471-2478
         for name, zz in (("kept", z), ("switched", z2)):
             dec_in = vae_definition.prepare_decoder_input(zz, C, sg["S"], None)    # history = previous window's (switched) z, :2481
-            idx = model.decoder.predict_note_indices(dec_in, batch_size=max(bs, n), sample_method=args.sample_method)    # :2482-2483, fused
+            dec = model.decoder.predict_descriptors(dec_in, batch_size=max(bs, n), sample_method=args.sample_method)    # :2482-2483, fused
+            idx = dec["notes"]
+            harm[name].append(dec["harmonicity"])                                                       # :2314-2317, :2537-2543
+            if name == "switched" and target in class_stats:
+                distances += [data_class.mahalanobis_distance(v, *class_stats[target]) for v in dec["signature"]]
             pred = np.argmax(clf.predict(idx, batch_size=bs), axis=1)
             if name == "kept":
                 kept += int(np.sum(pred == C))
@@ -67,7 +79,14 @@ def main():
         n_win += n
     dt = time.time() - t0
     print("%d windows: classified as their own style after autoencoding %.1f %%, as the TARGET style after the latent swap %.1f %% "
-          "(encode + 2 x decode + 2 x classify: %.0f windows/s)" % (n_win, 100.0 * kept / n_win, 100.0 * switched / n_win, n_win / dt))
+          "(encode + 2 x decode with descriptors + 2 x classify: %.0f windows/s)" % (n_win, 100.0 * kept / n_win, 100.0 * switched / n_win, n_win / dt))
+    with np.printoptions(precision=3, suppress=True):
+        for name in ("kept", "switched"):
+            print("mean harmonicity between the voices, %s decodes (NaN: the two voices never sound in the same segment):\n%s"
+                  % (name, descriptors.nanmean_windows(np.concatenate(harm[name], 0))))
+    if distances:
+        print("mean Mahalanobis distance of the switched decodes' signatures to the target style's training signatures: %.3f"
+              % float(np.mean(distances)))
 
 
 if __name__ == "__main__":

@@ -51,6 +51,20 @@ def songs_from_pickle_cache(path, s):
     return songs(X_tr, Y_tr, c_tr, I_tr, V_tr, D_tr), songs(X_te, Y_te, c_te, I_te, V_te, D_te)
 
 
+def attach_signatures(train, test, s, mode):
+    """the songs' ``S`` from their own windows (reference vae_training.py:668-716): the signature vector of every window of ``Y``,
+    normalised with the TRAINING set's mean and std (a std of 0 becomes 1e-10); test songs use the training statistics.  ``mode``
+    'device': mvae_desc_windows, one launch per song; 'host': the NumPy mirror.  Returns (mean, std)."""
+    from midi_vae_amd import descriptors
+    raw = [descriptors.signature_vectors(song["Y"], s, device=(mode == "device")) for song in train + test]
+    seen = np.concatenate(raw[:len(train)], 0)
+    mean, std = np.mean(seen, axis=0), np.std(seen, axis=0)
+    std[std == 0] = 1.0e-10
+    for song, sig in zip(train + test, raw):
+        song["S"] = (sig - mean) / std
+    return mean, std
+
+
 def history_for(model, song, s, use_encoder, on_device=True):
     """reference vae_training.py:788-798 - zeros in epoch 0, else the previous window's SAMPLED z (a fresh epsilon: one
     extra encoder forward per song in the reference).  ``on_device``: a deferred model.DeviceLatent - the draw is taken now, the
@@ -137,6 +151,9 @@ def main():
                     "test_paths.pickle) instead of synthetic songs")
     ap.add_argument("--batched-test", action="store_true", help="run the test pass of all songs as one chip-filling per-window "
                     "pass (autoencoder.evaluate_songs) instead of one evaluate call per song")
+    ap.add_argument("--signatures", default="zeros", choices=["zeros", "host", "device"], help="the songs' signature vectors S (target of "
+                    "the signature head, additional decoder input): 'zeros' as before; 'device' / 'host': computed from every window, "
+                    "on the MI355X or by the NumPy mirror, and normalised with the training set's statistics (reference :668-716)")
     args = ap.parse_args()
     s = vars(settings)
 
@@ -167,6 +184,12 @@ def main():
     else:
         train = synthetic_songs(args.songs, s, seed=1)         # the SAME songs on every rank (sharded inside fit)
         test = synthetic_songs(args.test_songs, s, seed=999)
+    if args.signatures != "zeros":
+        t0 = time.time()
+        mean_signature, _ = attach_signatures(train, test, s, args.signatures)
+        if rank == 0:
+            print("signature vectors of %d windows (%s): %.2f s; mean %s" % (
+                sum(sg["X"].shape[0] for sg in train + test), args.signatures, time.time() - t0, np.round(mean_signature, 4)))
     order_rng = np.random.default_rng(4321)                     # ... in the SAME order (the reference's shuffle is unseeded)
     path = os.path.join(args.model_path, "%s-_ls_inlen_%d_outlen_%d_beta_%s_lr_%s_lstmsize_%d_latent_%d" % (
         s["t"], s["input_length"], s["output_length"], s["beta"], s["learning_rate"], s["lstm_size"], s["latent_dim"]))
