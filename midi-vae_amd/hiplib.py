@@ -140,6 +140,22 @@ DESC_SIGNATURES = {
     "mvae_desc_windows": (_i32, [C.POINTER(DescArgs), _vp]),
 }
 
+
+class SweepArgs(C.Structure):
+    """mvae_sweep_args of include/midivae_sweep.h"""
+    _fields_ = [("idx", _vp), ("stride_t", _i64), ("stride_w", _i64), ("vel", _vp), ("n", _i32), ("T", _i32), ("voices", _i32),
+                ("silent", _i32), ("n_pitch", _i32), ("count_a", _i32), ("count_b", _i32), ("override_rules", _i32),
+                ("threshold", C.c_double), ("default_velocity", C.c_double), ("ld_out", _i32), ("reserved", _i32),
+                ("stats_out", _vp), ("vel_out", _vp)]
+
+
+SWEEP_ABI_VERSION = 1
+# the third header, include/midivae_sweep.h (versioned on its own, like the second)
+SWEEP_SIGNATURES = {
+    "mvae_sweep_abi_version": (_i32, []),
+    "mvae_sweep_windows": (_i32, [C.POINTER(SweepArgs), _vp]),
+}
+
 # name -> (restype, argtypes); every symbol include/midivae_hip.h declares
 SIGNATURES = {
     "mvae_abi_version": (_i32, []),
@@ -225,7 +241,7 @@ def load():
             "%s not found - build it with `make -C midi-vae_amd/csrc` (or __graft_entry__.build()); "
             "the MIDI-VAE engine has no CPU fallback" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(DESC_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(DESC_SIGNATURES.items()) + list(SWEEP_SIGNATURES.items()):
         fn = getattr(lib, name)      # AttributeError here = ABI drift between header and library
         fn.restype = res
         fn.argtypes = args
@@ -235,6 +251,9 @@ def load():
     if lib.mvae_desc_abi_version() != DESC_ABI_VERSION:
         raise HipLibraryMissing("descriptor ABI version mismatch: library %d, binding %d - rebuild with `make -C midi-vae_amd/csrc`"
                                 % (lib.mvae_desc_abi_version(), DESC_ABI_VERSION))
+    if lib.mvae_sweep_abi_version() != SWEEP_ABI_VERSION:
+        raise HipLibraryMissing("sweep ABI version mismatch: library %d, binding %d - rebuild with `make -C midi-vae_amd/csrc`"
+                                % (lib.mvae_sweep_abi_version(), SWEEP_ABI_VERSION))
     _lib = lib
     return lib
 

@@ -479,14 +479,17 @@ class Decoder(_ModelView):
                 i += 1
         return res
 
-    def _run(self, x, batch_size, want_probs=True, sample=None, all_heads=False, describe=None):
+    def _run(self, x, batch_size, want_probs=True, sample=None, all_heads=False, describe=None, sweep=None):
         """decoder forward over all windows at the forward-only engine's batch (``batch_size`` is the caller's: results are per
         window); every rank decodes everything it is given - decoding is pure replicas.
         ``sample``: the resolved arguments of a 'choice' decode (_sample_spec) - every engine batch is told the caller's index of
         its first window, so a window's draws do not depend on the batches.  ``all_heads``: the third result is a dict head ->
         indices of every softmax head (+ 'velocity').  ``describe``: descriptors.params(...) - the second result is a list of
-        descriptors.decoded_batch dicts, one per engine batch, instead of the concatenated note indices."""
+        descriptors.decoded_batch dicts, one per engine batch, instead of the concatenated note indices.  ``sweep``: a dict with
+        ``p`` = sweep.params(...) and ``return_rolls`` - the same with sweep.decoded_batch dicts, computed from the note, velocity
+        and instrument buffers of the decode."""
         sp = self._s.spec
+        want_vel = bool((all_heads or sweep is not None) and sp.meta_velocity)
         a = self._unpack(x)
         z = np.asarray(a.pop("z"))
         n = z.shape[0]
@@ -496,19 +499,26 @@ class Decoder(_ModelView):
             hi = min(n, lo + eng.maxB)
             B = hi - lo
             eng.stage_decoder_inputs(B, z=z[lo:hi], **{k: (None if v is None else np.asarray(v)[lo:hi]) for k, v in a.items()})
-            if sample is None and not all_heads:
+            if sample is None and not want_vel and not all_heads:
                 eng.decode(B, want_probs=want_probs)
             else:
                 spec = None
                 if sample is not None:
                     spec = dict(sample, first_window=lo, uniforms={k: u[lo:hi] for k, u in (sample.get("uniforms") or {}).items()})
-                eng.decode(B, want_probs=want_probs, sample=spec, want_velocity=all_heads and sp.meta_velocity)
+                eng.decode(B, want_probs=want_probs, sample=spec, want_velocity=want_vel)
             if want_probs:
                 outs.append(eng.outputs(B))
             if describe is not None:       # behind the decode on this stream, outside the step plans; one read per engine batch
                 from . import descriptors
                 rows = eng._v("notes.argmax" if sample is None else "notes.choice", sp.T, eng.pad16(B))
                 idxs.append(descriptors.decoded_batch(rows, B, describe))
+                continue
+            if sweep is not None:          # likewise: the statistics kernel reads the decode's own buffers
+                from . import sweep as sweep_mod
+                kind, Bp = ".argmax" if sample is None else ".choice", eng.pad16(B)
+                idxs.append(sweep_mod.decoded_batch(eng._v("notes" + kind, sp.T, Bp), eng._v("out.vel_p", sp.T, Bp) if want_vel else None,
+                                                    eng._v("instr" + kind, sp.V, Bp) if "instr" in self._s.head_names() else None,
+                                                    B, sweep["p"], sweep.get("return_rolls", False)))
                 continue
             if sample is None:
                 idxs.append(eng.note_indices(B))
@@ -520,7 +530,7 @@ class Decoder(_ModelView):
             if all_heads and sp.meta_velocity:
                 heads[-1]["velocity"] = eng.velocity(B)
         eng.check_pipeline()
-        if describe is not None:
+        if describe is not None or sweep is not None:
             return outs, idxs
         notes = np.concatenate(idxs, 0) if idxs else np.zeros((0, sp.T), np.uint8)
         if not all_heads:
@@ -614,6 +624,67 @@ class Decoder(_ModelView):
             return dict(notes=np.zeros((0, sp.T), np.uint8), signature=np.zeros((0, descriptors.SIGNATURE_LENGTH)),
                         harmonicity=np.zeros((0, sp.V, sp.V)))
         return {k: np.concatenate([d[k] for d in parts], 0) for k in ("notes", "signature", "harmonicity")}
+
+    def sweep_inputs(self, z, values, s):
+        """the decoder inputs of the n * Z * K windows of a latent sweep, in the order (sample, dimension, value): window (i, d, k)
+        is z[i] with coordinate d set to values[k]; C = 0, a zero signature and - the reference decodes every window in a call of
+        its own (vae_evaluation.py:1132-1140) - a zero history"""
+        from . import packers
+        sp = self._s.spec
+        z = np.asarray(z, np.float64)
+        if z.ndim != 2 or z.shape[1] != sp.Z:
+            raise ValueError("z must be (n, %d), got %r" % (sp.Z, z.shape))
+        n, Z, K = z.shape[0], sp.Z, len(values)
+        zs = np.repeat(z[:, None, None, :], Z, axis=1).repeat(K, axis=2)
+        zs[:, np.arange(Z), :, np.arange(Z)] = np.asarray(values, np.float64)
+        zs = zs.reshape(n * Z * K, Z)
+        return packers.prepare_decoder_input(s, zs, 0, np.zeros((n * Z * K, int(packers._g(s, "signature_vector_length")))),
+                                             np.zeros(zs.shape))
+
+    def latent_sweep(self, z, range_end_in_stds=1.0, sigma=1.0, evaluations_per_dimension=5, positive_and_negative=True,
+                     batch_size=32, sample_method="argmax", temperature=None, seed=None, return_rolls=False):
+        """The reference's latent_sweep_over_all_dimensions (vae_evaluation.py:1123-1213) without its plots: for every sample of
+        ``z`` (n, Z) and every latent dimension, decode the K windows in which that one coordinate takes the values of
+        sweep.sweep_values(...), and rank the dimensions by how the windows' pitch, velocity and instrument statistics move.  The
+        n * Z * K windows are decoded in the order (sample, dimension, value) with C = 0 and a zero signature; behind every engine
+        batch the statistics kernel (mvae_sweep_windows) runs on the decode's own buffers and the (B, 22) table plus the instrument
+        bytes come to the host in one copy - no (n, T) roll does unless ``return_rolls``.  Settings come from
+        ``decoder.sample_settings`` (None: the defaults of config.build_settings()).  dict: ``table`` (n, Z, K, 22) (columns:
+        sweep.COLUMNS), ``programs`` (n, Z, K, max_voices), ``values`` (K,), ``summaries[sample][dim]`` name -> (strength,
+        probability), ``influence`` name -> (Z,) array, ``most_peaked`` / ``overall_best`` name -> dimension; with ``return_rolls``
+        also ``notes`` (n, Z, K, T) uint8 and ``velocity`` (n, Z, K, T) float32 after the rules."""
+        from . import packers
+        from . import sweep as sweep_mod
+        s = self.sample_settings
+        if s is None:
+            from .config import build_settings
+            s = build_settings()
+        p, sp = sweep_mod.params(s), self._s.spec
+        if p["voices"] != sp.V:
+            raise ValueError("max_voices of the settings (%d) is not the model's (%d)" % (p["voices"], sp.V))
+        sweep_mod._check(sp.T, p)
+        values = np.asarray(sweep_mod.sweep_values(range_end_in_stds, sigma, evaluations_per_dimension, positive_and_negative))
+        z = np.asarray(z, np.float64)
+        x = self.sweep_inputs(z, values, s)
+        n, Z, K = z.shape[0], sp.Z, len(values)
+        if n == 0:
+            raise ValueError("z holds no sample")
+        N = n * Z * K
+        sample = self._sample_spec(N, sample_method, temperature, seed, None, self._softmax_heads())
+        parts = self._run(x, batch_size, want_probs=False, sample=sample, sweep=dict(p=p, return_rolls=return_rolls))[1]
+        table = np.concatenate([d["table"] for d in parts], 0).reshape(n, Z, K, sweep_mod.N_COLUMNS)
+        if parts and parts[0]["instr"] is not None:
+            programs = sweep_mod.programs_of(np.concatenate([d["instr"] for d in parts], 0),
+                                             packers._g(s, "instrument_attach_method")).reshape(n, Z, K, sp.V)
+        else:          # the reference's default I: all piano
+            programs = np.zeros((n, Z, K, sp.V), np.int64)
+        summaries, infl, peaked, best = sweep_mod.summarize_sweep(table, programs)
+        res = dict(table=table, programs=programs, values=values, summaries=summaries, influence=infl, most_peaked=peaked,
+                   overall_best=best)
+        if return_rolls:
+            res["notes"] = np.concatenate([d["notes"] for d in parts], 0).reshape(n, Z, K, sp.T)
+            res["velocity"] = np.concatenate([d["velocity"] for d in parts], 0).reshape(n, Z, K, sp.T)
+        return res
 
     def predict_indices(self, x, batch_size=32, sample_method="argmax", temperature=None, seed=None, uniforms=None):
         """The decoded index of EVERY softmax head - dict 'notes' (n, T), 'instr' (n, max_voices), 'held' (n, T), 'next' (n, T)
