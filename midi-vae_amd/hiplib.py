@@ -156,6 +156,21 @@ SWEEP_SIGNATURES = {
     "mvae_sweep_windows": (_i32, [C.POINTER(SweepArgs), _vp]),
 }
 
+class ReconArgs(C.Structure):
+    """mvae_recon_args of include/midivae_recon.h"""
+    _fields_ = [("idx", _vp), ("stride_t", _i64), ("stride_w", _i64), ("vel", _vp), ("held", _vp), ("orig", _vp),
+                ("orig_stride_t", _i64), ("orig_stride_w", _i64), ("first_window", _vp), ("n", _i32), ("T", _i32), ("voices", _i32),
+                ("silent", _i32), ("n_pitch", _i32), ("override_rules", _i32), ("threshold", C.c_double), ("carry", _vp),
+                ("vel_out", _vp), ("start_out", _vp), ("counts_out", _vp), ("ld_counts", _i32), ("reserved", _i32)]
+
+
+RECON_ABI_VERSION = 1
+# the fourth header, include/midivae_recon.h (versioned on its own, like the second and third)
+RECON_SIGNATURES = {
+    "mvae_recon_abi_version": (_i32, []),
+    "mvae_recon_songs": (_i32, [C.POINTER(ReconArgs), _vp]),
+}
+
 # name -> (restype, argtypes); every symbol include/midivae_hip.h declares
 SIGNATURES = {
     "mvae_abi_version": (_i32, []),
@@ -241,7 +256,8 @@ def load():
             "%s not found - build it with `make -C midi-vae_amd/csrc` (or __graft_entry__.build()); "
             "the MIDI-VAE engine has no CPU fallback" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(DESC_SIGNATURES.items()) + list(SWEEP_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(DESC_SIGNATURES.items()) + list(SWEEP_SIGNATURES.items()) + \
+            list(RECON_SIGNATURES.items()):
         fn = getattr(lib, name)      # AttributeError here = ABI drift between header and library
         fn.restype = res
         fn.argtypes = args
@@ -254,6 +270,9 @@ def load():
     if lib.mvae_sweep_abi_version() != SWEEP_ABI_VERSION:
         raise HipLibraryMissing("sweep ABI version mismatch: library %d, binding %d - rebuild with `make -C midi-vae_amd/csrc`"
                                 % (lib.mvae_sweep_abi_version(), SWEEP_ABI_VERSION))
+    if lib.mvae_recon_abi_version() != RECON_ABI_VERSION:
+        raise HipLibraryMissing("reconstruction ABI version mismatch: library %d, binding %d - rebuild with `make -C midi-vae_amd/csrc`"
+                                % (lib.mvae_recon_abi_version(), RECON_ABI_VERSION))
     _lib = lib
     return lib
 

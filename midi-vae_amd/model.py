@@ -479,7 +479,7 @@ class Decoder(_ModelView):
                 i += 1
         return res
 
-    def _run(self, x, batch_size, want_probs=True, sample=None, all_heads=False, describe=None, sweep=None):
+    def _run(self, x, batch_size, want_probs=True, sample=None, all_heads=False, describe=None, sweep=None, songs=None):
         """decoder forward over all windows at the forward-only engine's batch (``batch_size`` is the caller's: results are per
         window); every rank decodes everything it is given - decoding is pure replicas.
         ``sample``: the resolved arguments of a 'choice' decode (_sample_spec) - every engine batch is told the caller's index of
@@ -487,14 +487,24 @@ class Decoder(_ModelView):
         indices of every softmax head (+ 'velocity').  ``describe``: descriptors.params(...) - the second result is a list of
         descriptors.decoded_batch dicts, one per engine batch, instead of the concatenated note indices.  ``sweep``: a dict with
         ``p`` = sweep.params(...) and ``return_rolls`` - the same with sweep.decoded_batch dicts, computed from the note, velocity
-        and instrument buffers of the decode."""
+        and instrument buffers of the decode.  ``songs``: a dict that receives run-level window-major device tensors ``notes`` (n, T)
+        uint8 and, as far as the model has the heads, ``vel`` (n, T) float32, ``held`` (n, T) uint8 and ``instr`` (n, V) uint8 (None
+        otherwise): every engine batch's buffers are copied into them on the device, behind the decode; nothing is read back and
+        the second result is None."""
         sp = self._s.spec
-        want_vel = bool((all_heads or sweep is not None) and sp.meta_velocity)
+        want_vel = bool((all_heads or sweep is not None or songs is not None) and sp.meta_velocity)
         a = self._unpack(x)
         z = np.asarray(a.pop("z"))
         n = z.shape[0]
         eng = self._s.get_infer(n)
         outs, idxs, heads = [], [], []
+        if songs is not None:
+            import torch
+            has = self._s.head_names()
+            songs.update(notes=torch.empty((n, sp.T), dtype=torch.uint8, device=eng.device),
+                         vel=torch.empty((n, sp.T), dtype=torch.float32, device=eng.device) if want_vel else None,
+                         held=torch.empty((n, sp.T), dtype=torch.uint8, device=eng.device) if "held" in has else None,
+                         instr=torch.empty((n, sp.V), dtype=torch.uint8, device=eng.device) if "instr" in has else None)
         for lo in range(0, n, eng.maxB):
             hi = min(n, lo + eng.maxB)
             B = hi - lo
@@ -520,6 +530,16 @@ class Decoder(_ModelView):
                                                     eng._v("instr" + kind, sp.V, Bp) if "instr" in self._s.head_names() else None,
                                                     B, sweep["p"], sweep.get("return_rolls", False)))
                 continue
+            if songs is not None:          # likewise: transposing device copies into the run's rolls, a song may straddle engine batches
+                kind, Bp = ".argmax" if sample is None else ".choice", eng.pad16(B)
+                songs["notes"][lo:hi].copy_(eng._v("notes" + kind, sp.T, Bp)[:, :B].t())
+                if songs["vel"] is not None:
+                    songs["vel"][lo:hi].copy_(eng._v("out.vel_p", sp.T, Bp)[:, :B].t())
+                if songs["held"] is not None:
+                    songs["held"][lo:hi].copy_(eng._v("held" + kind, sp.T, Bp)[:, :B].t())
+                if songs["instr"] is not None:
+                    songs["instr"][lo:hi].copy_(eng._v("instr" + kind, sp.V, Bp)[:, :B].t())
+                continue
             if sample is None:
                 idxs.append(eng.note_indices(B))
                 if all_heads:
@@ -532,6 +552,8 @@ class Decoder(_ModelView):
         eng.check_pipeline()
         if describe is not None or sweep is not None:
             return outs, idxs
+        if songs is not None:
+            return outs, None
         notes = np.concatenate(idxs, 0) if idxs else np.zeros((0, sp.T), np.uint8)
         if not all_heads:
             return outs, notes
@@ -684,6 +706,76 @@ class Decoder(_ModelView):
         if return_rolls:
             res["notes"] = np.concatenate([d["notes"] for d in parts], 0).reshape(n, Z, K, sp.T)
             res["velocity"] = np.concatenate([d["velocity"] for d in parts], 0).reshape(n, Z, K, sp.T)
+        return res
+
+    def predict_songs(self, xs, batch_size=32, sample_method="argmax", temperature=None, seed=None, uniforms=None, originals=None):
+        """Decode whole songs and finish them on the device: ``xs`` is one decoder input list per song, as predict_indices takes them
+        (``prepare_decoder_input`` with the song's own history); all songs run as ONE chip-filling decode.  Every engine batch's note,
+        velocity and held buffers are copied on the device into window-major rolls of the whole run, and after the last batch
+        mvae_recon_songs (midi_vae_amd.reconstruction) runs once over all windows: the velocity post-rules with the per-voice state
+        carried from window to window of a song (reference vae_definition.py:1156-1190 on a whole song - a song may straddle engine
+        batches), the note starts, and eight counts per window.  One device-to-host read per array.  ``originals``: per song the
+        target notes as (n_i, T) indices (255 = no target) or one-hot rolls - the counts then compare against them and ``metrics``
+        holds the reference's reconstruction numbers (vae_evaluation.py:2211-2244, :2380-2415).  Settings come from
+        ``decoder.sample_settings`` (None: the defaults of config.build_settings()); a meta head on with meta_instrument off is
+        refused like packers.process_decoder_indices refuses it.  One dict per song: ``notes`` (n_i, T) uint8, ``velocity``
+        (n_i, T) float32 after the rules, ``starts`` (n_i, T) uint8 (0 = a note starts; all 1 for a model with neither a velocity
+        nor a held-notes head), ``instr`` (n_i, max_voices) uint8 where the model has the head, ``counts`` (n_i, 8) int32
+        (reconstruction.COUNTS) and, with ``originals``, ``metrics``.  Other arguments as predict_note_indices."""
+        import torch
+        from . import packers
+        from . import reconstruction as rec
+        from .descriptors import _as_rolls
+        s = self.sample_settings
+        if s is None:
+            from .config import build_settings
+            s = build_settings()
+        packers.refuse_meta_without_instrument(s)
+        p, sp = rec.params(s), self._s.spec
+        if p["voices"] != sp.V:
+            raise ValueError("max_voices of the settings (%d) is not the model's (%d)" % (p["voices"], sp.V))
+        rec._check(sp.T, p)
+        xs = [_as_list(x) for x in xs]
+        if not xs:
+            return []
+        if len({len(x) for x in xs}) != 1:
+            raise ValueError("predict_songs: every song must pass the same inputs, in the same order")
+        lengths = [np.asarray(x[1]).shape[0] for x in xs]
+        for i, m in enumerate(lengths):
+            if m <= 0:
+                raise ValueError("predict_songs: song %d has no windows - leave empty songs out of the list" % i)
+        orig = None
+        if originals is not None:
+            originals = [np.asarray(_as_rolls(o)) for o in originals]
+            if len(originals) != len(xs):
+                raise ValueError("predict_songs: %d originals for %d songs" % (len(originals), len(xs)))
+            for i, (o, m) in enumerate(zip(originals, lengths)):
+                if o.shape != (m, sp.T):
+                    raise ValueError("predict_songs: the original of song %d has shape %r, expected %r" % (i, o.shape, (m, sp.T)))
+            orig = np.concatenate(originals, 0)
+        x = [np.concatenate([np.asarray(xi[k]) for xi in xs], 0) for k in range(len(xs[0]))]
+        n = int(sum(lengths))
+        sample = self._sample_spec(n, sample_method, temperature, seed, uniforms, self._softmax_heads())
+        rolls = {}
+        self._run(x, batch_size, want_probs=False, sample=sample, songs=rolls)
+        dev = rolls["notes"].device
+        with torch.cuda.device(dev):
+            first = torch.from_numpy(rec.first_windows(lengths, n)).to(dev)
+            outs = rec.run_on_device(rolls["notes"], rolls["vel"], rolls["held"], None if orig is None else torch.from_numpy(orig).to(dev),
+                                     first, p)
+            velocity, starts, counts = (t.cpu().numpy() for t in outs)
+            notes = rolls["notes"].cpu().numpy()
+            instr = None if rolls["instr"] is None else rolls["instr"].cpu().numpy()
+        metrics = rec.song_metrics(counts, lengths, sp.T, s) if orig is not None else None
+        res, lo = [], 0
+        for i, m in enumerate(lengths):
+            d = dict(notes=notes[lo:lo + m], velocity=velocity[lo:lo + m], starts=starts[lo:lo + m], counts=counts[lo:lo + m])
+            if instr is not None:
+                d["instr"] = instr[lo:lo + m]
+            if metrics is not None:
+                d["metrics"] = metrics[i]
+            res.append(d)
+            lo += m
         return res
 
     def predict_indices(self, x, batch_size=32, sample_method="argmax", temperature=None, seed=None, uniforms=None):

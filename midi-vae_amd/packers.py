@@ -328,6 +328,14 @@ def process_decoder_outputs(s, decoder_outputs, sample_method):
     return Y, I, V, D, N
 
 
+def refuse_meta_without_instrument(s):
+    """what process_decoder_indices and decoder.predict_songs refuse: a meta head on with ``meta_instrument`` off"""
+    metas = [f for f in ("meta_velocity", "meta_held_notes", "meta_next_notes") if _g(s, f)]
+    if metas and not _g(s, "meta_instrument"):
+        raise NotImplementedError("process_decoder_indices with %s on and meta_instrument off: the reference decodes that "
+                                  "head as the instrument head" % metas[0])
+
+
 def process_decoder_indices(s, indices):
     """``process_decoder_outputs`` from decoded INDICES (``decoder.predict_indices``: dict 'notes' (n, T), and as far as the model
     has the heads 'instr' (n, max_voices), 'velocity' (n, T) float, 'held' (n, T), 'next' (n, T)) -> (Y, I, V, D, N): exactly what
@@ -336,10 +344,7 @@ def process_decoder_indices(s, indices):
     The reference reads element 1 of the output list as the instrument head whenever ANY meta head is on (:1131-1225); with
     ``meta_instrument`` off and another meta head on that decodes the wrong head, and is refused here."""
     T = _g(s, "output_length")
-    metas = [f for f in ("meta_velocity", "meta_held_notes", "meta_next_notes") if _g(s, f)]
-    if metas and not _g(s, "meta_instrument"):
-        raise NotImplementedError("process_decoder_indices with %s on and meta_instrument off: the reference decodes that "
-                                  "head as the instrument head" % metas[0])
+    refuse_meta_without_instrument(s)
     Y = notes_from_indices(s, np.asarray(indices["notes"]).astype(np.int64), _g(s, "output_dim"))
     I = V = D = N = None
     if _g(s, "meta_instrument"):
