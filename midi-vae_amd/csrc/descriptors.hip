@@ -9,85 +9,33 @@
 // an 8-byte one on banks 2l, 2l + 1 of 64 - conflict-free - and nothing lands in scratch (the Makefile checks it).  The rest
 // (counts, exact integer sums) stays in registers.
 //
-// Reading the rows: in a time-major (T, Bp) buffer (stride_w == 1) adjacent lanes read adjacent bytes, straight from memory.  Any
-// other layout - window-major (n, T) first of all - is staged through LDS in chunks of CHUNK_TICKS ticks: consecutive lanes fetch
-// consecutive rows of ONE window (contiguous when stride_t == 1) and the tile is read back [row][lane]; its rows are 65 bytes apart,
-// so the 64 stores of a fetch spread over the banks.
+// Reading the rows: Rows of rolls.h, in chunks of CHUNK_TICKS ticks - straight from memory in a time-major (T, Bp) buffer, staged
+// through LDS in any other layout, window-major (n, T) first of all.
 //
 // Arithmetic: counts, sums and sums of squares are integers (exact); max, min, mean and the ratios are one or two double divisions
 // in the reference's order (sum / count) / scale and so bit-equal to NumPy's; std = sqrt((c * sum(x^2) - sum(x)^2) / c^2).
-#include "common.h"
+#include "rolls.h"
 
 #include "../../include/midivae_descriptors.h"
 
 namespace {
 
-constexpr int LANES = 64;                  // one wave per workgroup: a window per lane
 constexpr int MAXV = MVAE_DESC_MAX_VOICES;
 constexpr int MAXHELD = 2 * MAXV;          // the held list keeps skipped notes: it settles below 2 * voices (see held update)
 constexpr int CHUNK_TICKS = 16;
-constexpr int TILE_LD = LANES + 1;
 constexpr int MAX_T = 1 << 20, MAX_LOW_CROP = 1023;      // c * sum(x^2) stays inside int64
+static_assert(MAXV == ROLL_MAX_VOICES, "rolls.h sizes its tiles for the headers' voice limit");
 
-// the rows of CHUNK_TICKS ticks of the workgroup's 64 windows
 template <bool STAGED>
-struct Rows {
-    const mvae_desc_args& a;
-    uint8_t* tile;
-    const int lane, w0;
-    __device__ Rows(const mvae_desc_args& a_, uint8_t* tile_) : a(a_), tile(tile_), lane(threadIdx.x), w0(blockIdx.x * LANES) {}
-
-    // before the ticks [tick0, tick0 + nt) are read (every lane of the workgroup calls it)
-    __device__ void open(int tick0, int nt) {
-        if (!STAGED) return;
-        const int rows = nt * a.voices;
-        const int nw = min(LANES, a.n - w0);
-        __syncthreads();          // the previous chunk has been read
-        for (int i = lane; i < nw * rows; i += LANES) {
-            const int wl = i / rows, r = i - wl * rows;
-            tile[r * TILE_LD + wl] = a.idx[(size_t)(tick0 * a.voices + r) * a.stride_t + (size_t)(w0 + wl) * a.stride_w];
-        }
-        __syncthreads();
-    }
-    // row r of the open chunk, window w0 + lane (< n)
-    __device__ int get(int tick0, int r) const {
-        if (STAGED) return tile[r * TILE_LD + lane];
-        return a.idx[(size_t)(tick0 * a.voices + r) * a.stride_t + (size_t)(w0 + lane) * a.stride_w];
-    }
-};
-
-__device__ __forceinline__ bool sounding(const mvae_desc_args& a, int x) { return x != a.silent && x != 255 && x < a.n_pitch; }
-
-// count, max, min and the exact sums of a list of non-negative integers
-struct Stats {
-    long long c = 0, s = 0, q = 0;
-    int hi = 0, lo = 0x7fffffff;
-    __device__ void push(int x) {
-        ++c;
-        s += x;
-        q += (long long)x * x;
-        hi = max(hi, x);
-        lo = min(lo, x);
-    }
-    __device__ void store(double* out, double scale) const {
-        if (c == 0) {
-            out[0] = out[1] = out[2] = out[3] = 0.0;
-            return;
-        }
-        out[0] = (double)hi / scale;
-        out[1] = (double)lo / scale;
-        out[2] = ((double)s / (double)c) / scale;
-        out[3] = sqrt((double)(c * q - s * s) / (double)(c * c)) / scale;
-    }
-};
+using DescRows = Rows<mvae_desc_args, STAGED, false, CHUNK_TICKS>;          // no velocity tile
 
 template <bool STAGED>
 __global__ __launch_bounds__(LANES) void desc_signature_k(const mvae_desc_args a) {
     __shared__ int held[MAXHELD][LANES], age[MAXHELD][LANES], cur[MAXV][LANES], prev[MAXV][LANES], dist[MAXV][LANES];
-    __shared__ uint8_t tile[STAGED ? CHUNK_TICKS * MAXV * TILE_LD : 1];
+    __shared__ uint8_t tile[DescRows<STAGED>::TILE];
     const int l = threadIdx.x, V = a.voices, ticks = a.T / V;
     const bool live = blockIdx.x * LANES + l < a.n;
-    Rows<STAGED> rows(a, tile);
+    DescRows<STAGED> rows(a, tile);
     Stats pitches, intervals, durations;
     int nheld = 0, nprev = 0, poly = 0;
 
@@ -99,8 +47,8 @@ __global__ __launch_bounds__(LANES) void desc_signature_k(const mvae_desc_args a
             // the note set of the tick: the distinct sounding indices of the voices, ascending (the k-hot fold)
             int nc = 0;
             for (int v = 0; v < V; ++v) {
-                const int x = rows.get(tick0, k * V + v);
-                if (!sounding(a, x)) continue;
+                const int x = rows.idx(tick0, k * V + v);
+                if (!roll_sounding(a.silent, a.n_pitch, x)) continue;
                 int p = 0;
                 while (p < nc && cur[p][l] < x) ++p;
                 if (p < nc && cur[p][l] == x) continue;          // a pitch doubled across voices counts once
@@ -173,9 +121,9 @@ __global__ __launch_bounds__(LANES) void desc_signature_k(const mvae_desc_args a
     out[0] = (double)durations.c / (double)ticks;          // (notes still held at the window's end are not counted)
     out[1] = (double)pitches.c / (double)ticks;
     out[2] = (double)poly / (double)ticks;
-    pitches.store(out + 3, 127.0);
-    intervals.store(out + 7, 127.0);
-    durations.store(out + 11, 1.0);
+    pitches.store_scaled(out + 3, 127.0);
+    intervals.store_scaled(out + 7, 127.0);
+    durations.store_scaled(out + 11, 1.0);
 }
 
 template <bool STAGED>
@@ -183,11 +131,11 @@ __global__ __launch_bounds__(LANES) void desc_harmonicity_k(const mvae_desc_args
     constexpr int PAIRS = MAXV * (MAXV - 1) / 2;
     __shared__ double cent[MAXV * 6][LANES], psum[PAIRS][LANES], tonal[72];
     __shared__ int cnt[MAXV][LANES], pcnt[PAIRS][LANES];
-    __shared__ uint8_t tile[STAGED ? CHUNK_TICKS * MAXV * TILE_LD : 1];
+    __shared__ uint8_t tile[DescRows<STAGED>::TILE];
     const int l = threadIdx.x, V = a.voices, ticks = a.T / V, res = a.resolution;
     const int used = ticks / res * res, per = a.n_pitch / 12, pairs = V * (V - 1) / 2;
     const bool live = blockIdx.x * LANES + l < a.n;
-    Rows<STAGED> rows(a, tile);
+    DescRows<STAGED> rows(a, tile);
     for (int i = l; i < 72; i += LANES) tonal[i] = (double)a.tonal[i];
     for (int p = 0; p < pairs; ++p) {
         psum[p][l] = 0.0;
@@ -208,8 +156,8 @@ __global__ __launch_bounds__(LANES) void desc_harmonicity_k(const mvae_desc_args
                 }
             // a voice's chroma over the segment, times the tonal matrix: the sum of the columns of its sounding ticks
             for (int v = 0; v < V; ++v) {
-                const int x = rows.get(tick0, k * V + v);
-                if (!sounding(a, x)) continue;
+                const int x = rows.idx(tick0, k * V + v);
+                if (!roll_sounding(a.silent, a.n_pitch, x)) continue;
                 const int bin = x / per;
                 ++cnt[v][l];
                 for (int j = 0; j < 6; ++j) cent[v * 6 + j][l] += tonal[j * 12 + bin];
@@ -251,10 +199,8 @@ __global__ __launch_bounds__(LANES) void desc_harmonicity_k(const mvae_desc_args
 extern "C" int mvae_desc_abi_version(void) { return 1; }
 
 extern "C" int mvae_desc_windows(const mvae_desc_args* a, void* stream) {
-    if (!a || !a->idx || (!a->sig_out && !a->harm_out)) return MVAE_E_ARG;
-    if (a->n <= 0 || a->T <= 0 || a->resolution <= 0 || a->stride_t <= 0 || a->stride_w <= 0) return MVAE_E_ARG;
-    if (a->voices < 2 || a->voices > MAXV || a->T % a->voices) return MVAE_E_ARG;
-    if (a->n_pitch <= 0 || a->silent < -1 || a->silent > 255 || a->low_crop < 0) return MVAE_E_ARG;
+    if (roll_args_refused(a) || (!a->sig_out && !a->harm_out)) return MVAE_E_ARG;
+    if (a->resolution <= 0 || a->low_crop < 0) return MVAE_E_ARG;
     if (a->sig_out && a->ld_sig < MVAE_DESC_SIGNATURE_LENGTH) return MVAE_E_ARG;
     if (a->harm_out && (!a->tonal || a->n_pitch % 12)) return MVAE_E_ARG;
     if (a->n_pitch > MVAE_DESC_MAX_PITCH || a->T > MAX_T || a->low_crop > MAX_LOW_CROP) return MVAE_E_UNSUPPORTED;

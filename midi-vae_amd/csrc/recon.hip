@@ -20,18 +20,17 @@
 // Rows travel through LDS both ways, in chunks of CHUNK_TICKS ticks laid out [tick][lane]: a lane's byte and its neighbours' share a
 // dword (reads of one dword by several lanes are a broadcast, not a bank conflict), and the global side of every copy is contiguous
 // - along a window's rows for window-major arrays and for the two outputs, along the windows for time-major (T, Bp) buffers.
-#include "common.h"
+#include "rolls.h"
 
 #include "../../include/midivae_recon.h"
 
 namespace {
 
 constexpr int BLOCK = 256;
-constexpr int MAXV = MVAE_RECON_MAX_VOICES, MAXP = MVAE_RECON_MAX_PITCH, MAX_T = MVAE_RECON_MAX_T;
+static_assert(MVAE_RECON_MAX_VOICES == ROLL_MAX_VOICES, "rolls.h refuses more voices than the header's limit");
+constexpr int MAXP = MVAE_RECON_MAX_PITCH, MAX_T = MVAE_RECON_MAX_T;
 constexpr int CHUNK_TICKS = 8;
 constexpr int NCOUNT = 6;          // what a lane counts: columns 0, 1, 2, 5, 6, 7
-
-__device__ __forceinline__ bool sounding(const mvae_recon_args& a, int x) { return x != a.silent && x != 255 && x < a.n_pitch; }
 
 // the workgroup's windows and this lane's place among them
 struct Place {
@@ -102,7 +101,7 @@ __global__ __launch_bounds__(BLOCK) void recon_carry_k(const mvae_recon_args a) 
         if (!p.live) continue;
         for (int k = 0; k < nt; ++k) {
             const int x = ti[k * BLOCK + l];
-            const bool snd = sounding(a, x);
+            const bool snd = roll_sounding(a.silent, a.n_pitch, x);
             const float v0 = snd ? tv[k * BLOCK + l] : 0.0f;
             pitch = snd ? x : -1;
             if (!((double)v0 < thr)) {
@@ -126,22 +125,26 @@ __global__ __launch_bounds__(BLOCK) void recon_apply_k(const mvae_recon_args a) 
     const float fallback = (float)(thr + (1.0 - thr) * 0.5);          // every row's velocity without the head
 
     // ---- what the song hands this (window, voice): a.carry is NULL where nothing is carried ----
-    int pp = -1;
-    float pv = 0.0f;
+    int pp0 = -1;
+    float pv0 = 0.0f;
     if (a.carry && p.live) {
         const uint2* rec = reinterpret_cast<const uint2*>(a.carry);
         const int fw = min(max(a.first_window[w], 0), w);
         if (w > fw) {
-            pp = (int)(rec[(size_t)(w - 1) * p.V + p.v].y & 0xffffu) - 1;
+            pp0 = (int)(rec[(size_t)(w - 1) * p.V + p.v].y & 0xffffu) - 1;
             for (int u = w - 1; u >= fw; --u) {
                 const uint2 r = rec[(size_t)u * p.V + p.v];
                 if (r.y >> 16) {
-                    pv = __uint_as_float(r.x);
+                    pv0 = __uint_as_float(r.x);
                     break;
                 }
             }
         }
     }
+    // the voice's state through this window, variables of its own: velocity_rule_step takes references, and with references to what the
+    // look-back loop assigns hipcc hoists that loop's velocity load behind it at a fifth more time per record
+    int pp = pp0;
+    float pv = pv0;
 
     int c_orig = 0, c_pred = 0, c_both = 0, c_start = 0, c_start_pred = 0, c_start_orig = 0;
     for (int tick0 = 0; tick0 < p.ticks; tick0 += CHUNK_TICKS) {
@@ -156,22 +159,12 @@ __global__ __launch_bounds__(BLOCK) void recon_apply_k(const mvae_recon_args a) 
             for (int k = 0; k < nt; ++k) {
                 const int at = k * BLOCK + l;
                 const int x = ti[at];
-                const bool snd = sounding(a, x);
+                const bool snd = roll_sounding(a.silent, a.n_pitch, x);
                 float out = fallback;
                 if (a.vel) {
                     const float v0 = snd ? tv[at] : 0.0f;
                     out = v0;
-                    if (rules) {
-                        const int pitch = snd ? x : -1;
-                        const bool vel_silent = (double)v0 < thr;
-                        if (vel_silent) {
-                            if (snd && pp > 0 && pp != pitch) out = pv;
-                        } else if (!snd) {
-                            out = 0.0f;
-                        }
-                        pp = pitch;
-                        if (!vel_silent) pv = v0;
-                    }
+                    out = rules ? velocity_rule_step(snd, x, v0, thr, pp, pv) : v0;
                 }
                 tv[at] = out;
                 int start = 1;
@@ -180,7 +173,7 @@ __global__ __launch_bounds__(BLOCK) void recon_apply_k(const mvae_recon_args a) 
                 else if (a.vel)
                     start = (double)out > thr ? 0 : 1;
                 th[at] = (uint8_t)start;
-                const bool osnd = a.orig != nullptr && sounding(a, to[at]);
+                const bool osnd = a.orig != nullptr && roll_sounding(a.silent, a.n_pitch, to[at]);
                 c_orig += osnd;
                 c_pred += snd;
                 c_both += osnd && snd && to[at] == x;
@@ -226,12 +219,8 @@ __global__ __launch_bounds__(BLOCK) void recon_apply_k(const mvae_recon_args a) 
 extern "C" int mvae_recon_abi_version(void) { return 1; }
 
 extern "C" int mvae_recon_songs(const mvae_recon_args* a, void* stream) {
-    if (!a || !a->idx || (!a->vel_out && !a->start_out && !a->counts_out)) return MVAE_E_ARG;
-    if (a->n <= 0 || a->T <= 0 || a->n_pitch <= 0 || a->stride_t <= 0 || a->stride_w <= 0) return MVAE_E_ARG;
+    if (roll_args_refused(a) || rule_args_refused(a) || (!a->vel_out && !a->start_out && !a->counts_out)) return MVAE_E_ARG;
     if (a->orig && (a->orig_stride_t <= 0 || a->orig_stride_w <= 0)) return MVAE_E_ARG;
-    if (a->voices < 2 || a->voices > MAXV || a->T % a->voices) return MVAE_E_ARG;
-    if (a->silent < -1 || a->silent > 255) return MVAE_E_ARG;
-    if (a->override_rules < 0 || a->override_rules > 1 || !(a->threshold - a->threshold == 0.0)) return MVAE_E_ARG;
     if (a->counts_out && a->ld_counts < MVAE_RECON_COUNTS) return MVAE_E_ARG;
     const bool carried = a->vel && a->override_rules && a->first_window;
     if (carried && !a->carry) return MVAE_E_ARG;

@@ -6,8 +6,7 @@
 // indexes dynamically - the tick's note set, the voices' previous pitch and velocity, a pitch histogram, the radix bins of the
 // velocity selection - lives in LDS laid out [slot][lane]; nothing lands in scratch (the Makefile checks it).
 //
-// Reading the rows: time-major (T, Bp) buffers (stride_w == 1) are read directly, adjacent lanes adjacent elements.  Any other
-// layout is staged through LDS in chunks of CHUNK_TICKS ticks, indices and velocities side by side (rows 65 elements apart).
+// Reading the rows: Rows of rolls.h in chunks of CHUNK_TICKS ticks, indices and velocities side by side.
 //
 // A window is walked several times; every walk re-runs the rule automaton, so nothing of size T is kept per lane:
 //   walk 1   pitch list (exact integer sums, a histogram for the median and the two counted columns), velocities after the rules
@@ -18,49 +17,20 @@
 //            unsigned order is the floats' order: 5 bits a walk from the top, counting the keys that share the prefix found so far;
 //   walk 9   only where a lane's count is even and its two middle elements differ: the smallest key above the lower one.
 // Walks 3..9 are skipped by a workgroup none of whose lanes needs them.
-#include "common.h"
+#include "rolls.h"
 
 #include "../../include/midivae_sweep.h"
 
 namespace {
 
-constexpr int LANES = 64;                  // one wave per workgroup: a window per lane
 constexpr int MAXV = MVAE_SWEEP_MAX_VOICES, MAXP = MVAE_SWEEP_MAX_PITCH;
 constexpr int CHUNK_TICKS = 8;
-constexpr int TILE_LD = LANES + 1;
 constexpr int MAX_T = MVAE_SWEEP_MAX_T;    // ticks <= 2^15 fit the 16-bit histogram; c * sum(t^2) < 2^16 * 2^48 / 3 stays inside int64
 constexpr int DIGIT_BITS = 5, DIGITS = 1 << DIGIT_BITS;
+static_assert(MAXV == ROLL_MAX_VOICES, "rolls.h sizes its tiles for the headers' voice limit");
 
-// the rows of CHUNK_TICKS ticks of the workgroup's 64 windows: index and velocity
 template <bool STAGED>
-struct Rows {
-    const mvae_sweep_args& a;
-    uint8_t* ti;
-    float* tv;
-    const int lane, w0;
-    __device__ Rows(const mvae_sweep_args& a_, uint8_t* ti_, float* tv_) : a(a_), ti(ti_), tv(tv_), lane(threadIdx.x), w0(blockIdx.x * LANES) {}
-
-    // before the ticks [tick0, tick0 + nt) are read (every lane of the workgroup calls it)
-    __device__ void open(int tick0, int nt) {
-        if (!STAGED) return;
-        const int rows = nt * a.voices;
-        const int nw = min(LANES, a.n - w0);
-        __syncthreads();          // the previous chunk has been read
-        for (int i = lane; i < nw * rows; i += LANES) {
-            const int wl = i / rows, r = i - wl * rows;
-            const size_t at = (size_t)(tick0 * a.voices + r) * a.stride_t + (size_t)(w0 + wl) * a.stride_w;
-            ti[r * TILE_LD + wl] = a.idx[at];
-            if (a.vel) tv[r * TILE_LD + wl] = a.vel[at];
-        }
-        __syncthreads();
-    }
-    __device__ size_t at(int tick0, int r) const { return (size_t)(tick0 * a.voices + r) * a.stride_t + (size_t)(w0 + lane) * a.stride_w; }
-    // row r of the open chunk, window w0 + lane (< n)
-    __device__ int idx(int tick0, int r) const { return STAGED ? ti[r * TILE_LD + lane] : a.idx[at(tick0, r)]; }
-    __device__ float vel(int tick0, int r) const { return STAGED ? tv[r * TILE_LD + lane] : a.vel[at(tick0, r)]; }
-};
-
-__device__ __forceinline__ bool sounding(const mvae_sweep_args& a, int x) { return x != a.silent && x != 255 && x < a.n_pitch; }
+using SweepRows = Rows<mvae_sweep_args, STAGED, true, CHUNK_TICKS>;          // index and velocity side by side
 
 // the floats' order as the unsigned order of 32-bit keys, and back
 __device__ __forceinline__ uint32_t key_of(float v) {
@@ -68,32 +38,6 @@ __device__ __forceinline__ uint32_t key_of(float v) {
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 __device__ __forceinline__ float float_of(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
-
-// count, max, min and the exact sums of a list of non-negative integers
-struct Stats {
-    long long c = 0, s = 0, q = 0;
-    int hi = 0, lo = 0x7fffffff;
-    __device__ void push(int x) {
-        ++c;
-        s += x;
-        q += (long long)x * x;
-        hi = max(hi, x);
-        lo = min(lo, x);
-    }
-    // mean, median, min, max, range, std
-    __device__ void store(double* out, double median) const {
-        if (c == 0) {
-            for (int i = 0; i < 6; ++i) out[i] = __builtin_nan("");
-            return;
-        }
-        out[0] = (double)s / (double)c;
-        out[1] = median;
-        out[2] = (double)lo;
-        out[3] = (double)hi;
-        out[4] = (double)(hi - lo);
-        out[5] = sqrt((double)(c * q - s * s) / (double)(c * c));
-    }
-};
 
 struct Lds {
     int (*cur)[LANES];
@@ -104,7 +48,7 @@ struct Lds {
 // One walk over the window of this lane: note(x) for every distinct sounding index of a tick (only with PITCH), row(t, v) for every
 // row with its velocity after the rules.  Every lane of the workgroup calls it; lanes that are not live only help staging.
 template <bool STAGED, bool PITCH, class NoteF, class RowF>
-__device__ __forceinline__ void walk(const mvae_sweep_args& a, Rows<STAGED>& rows, const Lds& m, bool live, NoteF&& note, RowF&& row) {
+__device__ __forceinline__ void walk(const mvae_sweep_args& a, SweepRows<STAGED>& rows, const Lds& m, bool live, NoteF&& note, RowF&& row) {
     const int l = threadIdx.x, V = a.voices, ticks = a.T / V;
     const bool rules = a.vel != nullptr && a.override_rules != 0;
     if (rules)
@@ -121,7 +65,7 @@ __device__ __forceinline__ void walk(const mvae_sweep_args& a, Rows<STAGED>& row
             for (int v = 0; v < V; ++v) {
                 const int r = k * V + v;
                 const int x = rows.idx(tick0, r);
-                const bool snd = sounding(a, x);
+                const bool snd = roll_sounding(a.silent, a.n_pitch, x);
                 if (PITCH && snd) {          // the k-hot fold: a pitch doubled across voices counts once
                     bool dup = false;
                     for (int j = 0; j < nc; ++j) dup = dup || m.cur[j][l] == x;
@@ -132,21 +76,9 @@ __device__ __forceinline__ void walk(const mvae_sweep_args& a, Rows<STAGED>& row
                 }
                 double vel = a.default_velocity;
                 if (a.vel) {
-                    vel = snd ? (double)rows.vel(tick0, r) : 0.0;
-                    if (rules) {
-                        const int pitch = snd ? x : -1;
-                        const bool vel_silent = vel < a.threshold;
-                        double out = vel;
-                        if (vel_silent) {
-                            const int before = m.pp[v][l];
-                            if (snd && before > 0 && before != pitch) out = (double)m.pv[v][l];
-                        } else if (!snd) {
-                            out = 0.0;
-                        }
-                        m.pp[v][l] = pitch;
-                        if (!vel_silent) m.pv[v][l] = (float)vel;          // (a float widened: exact)
-                        vel = out;
-                    }
+                    const float v0 = snd ? rows.vel(tick0, r) : 0.0f;
+                    // the voice's state stays in its LDS slots; the rule's float is widened afterwards, which is exact
+                    vel = (double)(rules ? velocity_rule_step(snd, x, v0, a.threshold, m.pp[v][l], m.pv[v][l]) : v0);
                 }
                 row((tick0 + k) * V + v, vel);
             }
@@ -160,14 +92,14 @@ __global__ __launch_bounds__(LANES) void sweep_windows_k(const mvae_sweep_args a
     __shared__ float pv[MAXV][LANES];
     __shared__ uint16_t hist[MAXP][LANES];
     __shared__ uint32_t bins[DIGITS][LANES];
-    __shared__ uint8_t ti[STAGED ? CHUNK_TICKS * MAXV * TILE_LD : 1];
-    __shared__ float tv[STAGED ? CHUNK_TICKS * MAXV * TILE_LD : 1];
+    __shared__ uint8_t ti[SweepRows<STAGED>::TILE];
+    __shared__ float tv[SweepRows<STAGED>::TILE];
     __shared__ int more;
     const int l = threadIdx.x, T = a.T;
     const int w = blockIdx.x * LANES + l;
     const bool live = w < a.n;
     const double thr = a.threshold;
-    Rows<STAGED> rows(a, ti, tv);
+    SweepRows<STAGED> rows(a, ti, tv);
     const Lds m{cur, pp, pv};
 
     // ---- walk 1 ----
@@ -209,7 +141,7 @@ __global__ __launch_bounds__(LANES) void sweep_windows_k(const mvae_sweep_args a
             median = (double)(m_lo + m_hi) / 2.0;
         }
         out[0] = (double)pitches.c;
-        pitches.store(out + 1, median);
+        pitches.store_six(out + 1, median);
         out[7] = a.count_a < a.n_pitch ? (double)hist[a.count_a][l] : 0.0;
         out[8] = a.count_b < a.n_pitch ? (double)hist[a.count_b][l] : 0.0;
         out[9] = (double)c;
@@ -234,7 +166,7 @@ __global__ __launch_bounds__(LANES) void sweep_windows_k(const mvae_sweep_args a
         if (select) ++bins[key_of((float)v) >> (32 - DIGIT_BITS)][l];
     });
     if (live) {
-        starts.store(out + 16, (double)(p_lo + p_hi) / 2.0);
+        starts.store_six(out + 16, (double)(p_lo + p_hi) / 2.0);
         if (c == 0) {
             for (int i = 10; i < 16; ++i) out[i] = __builtin_nan("");
         } else {
@@ -302,11 +234,8 @@ __global__ __launch_bounds__(LANES) void sweep_windows_k(const mvae_sweep_args a
 extern "C" int mvae_sweep_abi_version(void) { return 1; }
 
 extern "C" int mvae_sweep_windows(const mvae_sweep_args* a, void* stream) {
-    if (!a || !a->idx || (!a->stats_out && !a->vel_out)) return MVAE_E_ARG;
-    if (a->n <= 0 || a->T <= 0 || a->n_pitch <= 0 || a->stride_t <= 0 || a->stride_w <= 0) return MVAE_E_ARG;
-    if (a->voices < 2 || a->voices > MAXV || a->T % a->voices) return MVAE_E_ARG;
-    if (a->silent < -1 || a->silent > 255 || a->count_a < 0 || a->count_a > 255 || a->count_b < 0 || a->count_b > 255) return MVAE_E_ARG;
-    if (a->override_rules < 0 || a->override_rules > 1 || !(a->threshold - a->threshold == 0.0)) return MVAE_E_ARG;
+    if (roll_args_refused(a) || rule_args_refused(a) || (!a->stats_out && !a->vel_out)) return MVAE_E_ARG;
+    if (a->count_a < 0 || a->count_a > 255 || a->count_b < 0 || a->count_b > 255) return MVAE_E_ARG;
     if (a->stats_out && a->ld_out < MVAE_SWEEP_COLUMNS) return MVAE_E_ARG;
     if (a->n_pitch > MAXP || a->T > MAX_T) return MVAE_E_UNSUPPORTED;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);

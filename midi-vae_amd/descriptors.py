@@ -26,15 +26,14 @@ import numpy as np
 
 from . import hiplib as hl
 from .packers import _g
+from .rolls import HostPack, as_rolls, base_params, check_rows, device_roll, host_roll, sounding
 
 SIGNATURE_LENGTH = 15
 
 
 def params(s):
     """what the descriptors read from the settings"""
-    n_pitch = int(_g(s, "high_crop")) - int(_g(s, "low_crop"))
-    return dict(voices=int(_g(s, "max_voices")), n_pitch=n_pitch, silent=n_pitch if _g(s, "include_silent_note") else -1,
-                low_crop=int(_g(s, "low_crop")), resolution=int(_g(s, "SMALLEST_NOTE")) // 4)
+    return dict(base_params(s), low_crop=int(_g(s, "low_crop")), resolution=int(_g(s, "SMALLEST_NOTE")) // 4)
 
 
 def tonal_matrix(r1=1.0, r2=1.0, r3=0.5):
@@ -105,15 +104,10 @@ def signature_from_note_sets(song, _tidy=False, _np_std=False):
             _stats(intervals, 127, _np_std) + _stats(durations, 1.0, _np_std))
 
 
-def _sounding(idx, p):
-    idx = np.asarray(idx)
-    return (idx != p["silent"]) & (idx != 255) & (idx < p["n_pitch"])
-
-
 def _mirror_signatures(idx, p, _tidy=False, _np_std=False):
     n, T = idx.shape
     V = p["voices"]
-    on = _sounding(idx, p)
+    on = sounding(idx, p)
     pitch = idx.astype(np.int64) + p["low_crop"]
     out = np.zeros((n, SIGNATURE_LENGTH))
     for w in range(n):
@@ -135,7 +129,7 @@ def _mirror_harmonicity(idx, p):
     if p["n_pitch"] % 12:
         raise ValueError("harmonicity needs a pitch range that is a multiple of 12 columns, got %d" % p["n_pitch"])
     use = idx[:, :segs * res * V].reshape(n, segs, res, V)
-    on = _sounding(use, p)
+    on = sounding(use, p)
     bins = np.where(on, use // (p["n_pitch"] // 12), 12)
     chroma = (bins[..., None] == np.arange(12)).sum(2).astype(np.float64)          # (n, segs, V, 12)
     total = chroma.sum(-1)
@@ -173,39 +167,15 @@ def enqueue(ptr, stride_t, stride_w, n, T, p, sig_out, harm_out, tonal, stream):
     hl.check(hl.load().mvae_desc_windows(C.byref(a), stream), "mvae_desc_windows")
 
 
-def _as_rolls(idx):
-    """(n, T) uint8 index rolls from index rolls or (n, T, K) one-hot rolls; device tensors pass through"""
-    if hasattr(idx, "data_ptr"):
-        return idx
-    idx = np.asarray(idx)
-    if idx.ndim == 3:
-        from .staging import host_onehot_to_index
-        return host_onehot_to_index(idx, "piano roll")
-    if idx.ndim != 2:
-        raise ValueError("expected (n, T) index rolls or (n, T, K) one-hot rolls, got %s" % (idx.shape,))
-    if idx.dtype != np.uint8:
-        if idx.size and (idx.min() < 0 or idx.max() > 255):
-            raise ValueError("indices must fit one byte")
-        idx = idx.astype(np.uint8)
-    return idx
-
-
 def _check(T, p, harm):
-    V = p["voices"]
-    if not 2 <= V <= 8 or T % V:
-        raise ValueError("rows per window (%d) must be a multiple of max_voices (%d, 2..8)" % (T, V))
+    check_rows(T, p)
     if harm and p["n_pitch"] % 12:
         raise ValueError("harmonicity needs a pitch range that is a multiple of 12 columns, got %d" % p["n_pitch"])
 
 
 def _device_run(idx, p, want_sig, want_harm, device=None):
     import torch
-    if hasattr(idx, "data_ptr"):
-        t = idx
-        if t.dtype != torch.uint8 or t.dim() != 2 or not t.is_cuda:
-            raise ValueError("a device roll is a 2-D uint8 tensor (n, T), any strides")
-    else:
-        t = torch.from_numpy(np.ascontiguousarray(idx)).to(device or "cuda")
+    t = device_roll(idx, torch.uint8, "notes", device=device)
     n, T = t.shape
     V = p["voices"]
     _check(T, p, want_harm)
@@ -223,39 +193,34 @@ def decoded_batch(rows, B, p):
     dict ``notes`` (B, T) uint8, ``signature`` (B, 15), ``harmonicity`` (B, V, V).  Enqueued on the current stream of the buffer's
     device; the three results travel to the host in ONE copy."""
     import torch
-    T, Bp = rows.shape
-    V = p["voices"]
-    nb_sig, nb_harm = B * SIGNATURE_LENGTH * 8, B * V * V * 8
-    pack = torch.empty(nb_sig + nb_harm + B * T, dtype=torch.uint8, device=rows.device)
-    sig = pack[:nb_sig].view(torch.float64).view(B, SIGNATURE_LENGTH)
-    harm = pack[nb_sig:nb_sig + nb_harm].view(torch.float64).view(B, V * V)
+    T, V = rows.shape[0], p["voices"]
+    pack = HostPack(rows.device, [("signature", torch.float64, (B, SIGNATURE_LENGTH)), ("harmonicity", torch.float64, (B, V * V)),
+                                  ("notes", torch.uint8, (B, T))])
     with torch.cuda.device(rows.device):
-        enqueue(rows.data_ptr(), rows.stride(0), rows.stride(1), B, T, p, sig, harm, _tonal_on(rows.device),
-                torch.cuda.current_stream().cuda_stream)
-        pack[nb_sig + nb_harm:].view(B, T).copy_(rows[:, :B].t())
-        host = pack.cpu().numpy()
-    return dict(notes=host[nb_sig + nb_harm:].reshape(B, T).copy(), signature=host[:nb_sig].view(np.float64).reshape(B, SIGNATURE_LENGTH).copy(),
-                harmonicity=host[nb_sig:nb_sig + nb_harm].view(np.float64).reshape(B, V, V).copy())
+        enqueue(rows.data_ptr(), rows.stride(0), rows.stride(1), B, T, p, pack.views["signature"], pack.views["harmonicity"],
+                _tonal_on(rows.device), torch.cuda.current_stream().cuda_stream)
+        pack.views["notes"].copy_(rows[:, :B].t())
+        res = pack.to_host()
+    res["harmonicity"] = res["harmonicity"].reshape(B, V, V)
+    return res
 
 
 def signature_vectors(idx, s, device=True, _tidy=False, _np_std=False):
     """(n, 15) float64 signature vectors of (n, T) uint8 index rolls, (n, T, K) one-hot rolls or a 2-D uint8 device tensor"""
-    p, idx = params(s), _as_rolls(idx)
+    p, idx = params(s), as_rolls(idx)
     if device:
         return _device_run(idx, p, True, False)[0]
-    if hasattr(idx, "data_ptr"):
-        idx = idx.cpu().numpy()
+    idx = host_roll(idx, np.uint8, "notes")
     _check(idx.shape[1], p, False)
     return _mirror_signatures(idx, p, _tidy, _np_std)
 
 
 def harmonicity(idx, s, device=True):
     """(n, V, V) float64 tonal distance between the voices of every window; NaN where two voices never sound in the same segment"""
-    p, idx = params(s), _as_rolls(idx)
+    p, idx = params(s), as_rolls(idx)
     if device:
         return _device_run(idx, p, False, True)[1]
-    if hasattr(idx, "data_ptr"):
-        idx = idx.cpu().numpy()
+    idx = host_roll(idx, np.uint8, "notes")
     _check(idx.shape[1], p, True)
     return _mirror_harmonicity(idx, p)
 

@@ -1407,23 +1407,6 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
         self._sample_mode = (frozenset(supplied), tries if supplied else 0)
         return ("choice",) + self._sample_mode
 
-    def sampled_indices(self, B):
-        """head name -> (B, T_head) uint8: what the last ``decode(..., sample=...)`` drew for every softmax decoder head"""
-        Bp = self.pad16(B)
-        return {h.name: self._v(h.name + ".choice", h.T, Bp)[:, :B].t().contiguous().cpu().numpy()
-                for h in self.dec_heads if h.kind == 0}
-
-    def argmax_indices(self, B):
-        """the same from the heads' own first-maximum indices (every decode without ``sample`` writes them)"""
-        Bp = self.pad16(B)
-        return {h.name: self._v(h.name + ".argmax", h.T, Bp)[:, :B].t().contiguous().cpu().numpy()
-                for h in self.dec_heads if h.kind == 0}
-
-    def velocity(self, B):
-        """(B, T) float32 output of the velocity head of the last decode run with ``want_probs`` or ``want_velocity``"""
-        h = self.head["vel"]
-        return self._v("out.vel_p", h.T, self.pad16(B))[:, :B].t().contiguous().cpu().numpy()
-
     def _decode(self, B, want_probs):
         self._have_targets = False
         self._S_done = False

@@ -257,9 +257,37 @@ class Results(object):
             out[a.key] = self._v("out.%s_p" % a.key, Bp, s.C)[:B].cpu().numpy()
         return out
 
+    def decoded(self, B, sampled):
+        """what the last decode left, as time-major (T_head, Bp) device views (columns B.. are padding): head name -> uint8 indices of
+        every softmax decoder head - the draws of ``decode(..., sample=...)`` if ``sampled``, else the heads' own first maxima, which
+        every decode without ``sample`` writes - plus 'velocity' -> the float32 output of the velocity head where the model has one
+        (valid after a decode with ``want_probs`` or ``want_velocity``).  The one place that names these buffers."""
+        Bp, kind = self.pad16(B), ".choice" if sampled else ".argmax"
+        views = {h.name: self._v(h.name + kind, h.T, Bp) for h in self.dec_heads if h.kind == 0}
+        if "vel" in self.head:
+            views["velocity"] = self._v("out.vel_p", self.head["vel"].T, Bp)
+        return views
+
+    @staticmethod
+    def rows_to_host(view, B):
+        """the first ``B`` columns of a time-major view as a window-major host array"""
+        return view[:, :B].t().contiguous().cpu().numpy()
+
     def note_indices(self, B):
         """(B,T) uint8 argmax note index per row - the fused form of sample_vector(...,'argmax')."""
-        return self._v("notes.argmax", self.spec.T, self.pad16(B))[:, :B].t().contiguous().cpu().numpy()
+        return self.rows_to_host(self.decoded(B, False)["notes"], B)
+
+    def sampled_indices(self, B, sampled=True):
+        """head name -> (B, T_head) uint8: what the last ``decode(..., sample=...)`` drew for every softmax decoder head"""
+        return {k: self.rows_to_host(v, B) for k, v in self.decoded(B, sampled).items() if k != "velocity"}
+
+    def argmax_indices(self, B):
+        """the same from the heads' own first-maximum indices"""
+        return self.sampled_indices(B, False)
+
+    def velocity(self, B):
+        """(B, T) float32 output of the velocity head of the last decode run with ``want_probs`` or ``want_velocity``"""
+        return self.rows_to_host(self.decoded(B, False)["velocity"], B)
 
     def latent(self, B):
         return self._v("zh", self.pad16(B), self.spec.zin)[:B, :self.spec.Z].cpu().numpy()

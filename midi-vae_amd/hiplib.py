@@ -239,6 +239,12 @@ SIGNATURES = {
     "mvae_host_rows_to_tm_f32": (_i32, [_vp, _i32, _i64, _i32, _i64, _i64, _f32, _vp, _i32]),
 }
 
+# the four headers under include/: (what its message calls it, version symbol, version constant, signatures)
+HEADERS = (("", "mvae_abi_version", ABI_VERSION, SIGNATURES),
+           ("descriptor ", "mvae_desc_abi_version", DESC_ABI_VERSION, DESC_SIGNATURES),
+           ("sweep ", "mvae_sweep_abi_version", SWEEP_ABI_VERSION, SWEEP_SIGNATURES),
+           ("reconstruction ", "mvae_recon_abi_version", RECON_ABI_VERSION, RECON_SIGNATURES))
+
 _lib = None
 
 
@@ -256,23 +262,15 @@ def load():
             "%s not found - build it with `make -C midi-vae_amd/csrc` (or __graft_entry__.build()); "
             "the MIDI-VAE engine has no CPU fallback" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(DESC_SIGNATURES.items()) + list(SWEEP_SIGNATURES.items()) + \
-            list(RECON_SIGNATURES.items()):
-        fn = getattr(lib, name)      # AttributeError here = ABI drift between header and library
-        fn.restype = res
-        fn.argtypes = args
-    if lib.mvae_abi_version() != ABI_VERSION:
-        raise HipLibraryMissing("ABI version mismatch: library %d, binding %d - rebuild with `make -C midi-vae_amd/csrc`"
-                                % (lib.mvae_abi_version(), ABI_VERSION))
-    if lib.mvae_desc_abi_version() != DESC_ABI_VERSION:
-        raise HipLibraryMissing("descriptor ABI version mismatch: library %d, binding %d - rebuild with `make -C midi-vae_amd/csrc`"
-                                % (lib.mvae_desc_abi_version(), DESC_ABI_VERSION))
-    if lib.mvae_sweep_abi_version() != SWEEP_ABI_VERSION:
-        raise HipLibraryMissing("sweep ABI version mismatch: library %d, binding %d - rebuild with `make -C midi-vae_amd/csrc`"
-                                % (lib.mvae_sweep_abi_version(), SWEEP_ABI_VERSION))
-    if lib.mvae_recon_abi_version() != RECON_ABI_VERSION:
-        raise HipLibraryMissing("reconstruction ABI version mismatch: library %d, binding %d - rebuild with `make -C midi-vae_amd/csrc`"
-                                % (lib.mvae_recon_abi_version(), RECON_ABI_VERSION))
+    for what, version, want, signatures in HEADERS:
+        for name, (res, args) in signatures.items():
+            fn = getattr(lib, name)      # AttributeError here = ABI drift between header and library
+            fn.restype = res
+            fn.argtypes = args
+        have = getattr(lib, version)()
+        if have != want:
+            raise HipLibraryMissing("%sABI version mismatch: library %d, binding %d - rebuild with `make -C midi-vae_amd/csrc`"
+                                    % (what, have, want))
     _lib = lib
     return lib
 

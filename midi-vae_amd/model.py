@@ -28,6 +28,7 @@ from collections import OrderedDict
 
 import numpy as np
 
+from . import decode_sinks as sinks
 from .layout import ModelSpec, ParamLayout, init_params, spec_from_create_kwargs
 
 
@@ -479,94 +480,43 @@ class Decoder(_ModelView):
                 i += 1
         return res
 
-    def _run(self, x, batch_size, want_probs=True, sample=None, all_heads=False, describe=None, sweep=None, songs=None):
+    def _run(self, x, batch_size, sink, sample=None):
         """decoder forward over all windows at the forward-only engine's batch (``batch_size`` is the caller's: results are per
-        window); every rank decodes everything it is given - decoding is pure replicas.
-        ``sample``: the resolved arguments of a 'choice' decode (_sample_spec) - every engine batch is told the caller's index of
-        its first window, so a window's draws do not depend on the batches.  ``all_heads``: the third result is a dict head ->
-        indices of every softmax head (+ 'velocity').  ``describe``: descriptors.params(...) - the second result is a list of
-        descriptors.decoded_batch dicts, one per engine batch, instead of the concatenated note indices.  ``sweep``: a dict with
-        ``p`` = sweep.params(...) and ``return_rolls`` - the same with sweep.decoded_batch dicts, computed from the note, velocity
-        and instrument buffers of the decode.  ``songs``: a dict that receives run-level window-major device tensors ``notes`` (n, T)
-        uint8 and, as far as the model has the heads, ``vel`` (n, T) float32, ``held`` (n, T) uint8 and ``instr`` (n, V) uint8 (None
-        otherwise): every engine batch's buffers are copied into them on the device, behind the decode; nothing is read back and
-        the second result is None."""
-        sp = self._s.spec
-        want_vel = bool((all_heads or sweep is not None or songs is not None) and sp.meta_velocity)
+        window); every rank decodes everything it is given - decoding is pure replicas.  ``sink`` (decode_sinks)
+        says what the decode keeps, takes every engine batch's device buffers behind the decode and makes the result.  ``sample``:
+        the resolved arguments of a 'choice' decode (_sample_spec) - every engine batch is told the caller's index of its first
+        window, so a window's draws do not depend on the batches.  Engine.decode keys its recorded step plans on the VALUES it is
+        given: without a sample and a velocity request this is the plain ``eng.decode(B, want_probs=...)`` and replays that plan."""
         a = self._unpack(x)
         z = np.asarray(a.pop("z"))
         n = z.shape[0]
         eng = self._s.get_infer(n)
-        outs, idxs, heads = [], [], []
-        if songs is not None:
-            import torch
-            has = self._s.head_names()
-            songs.update(notes=torch.empty((n, sp.T), dtype=torch.uint8, device=eng.device),
-                         vel=torch.empty((n, sp.T), dtype=torch.float32, device=eng.device) if want_vel else None,
-                         held=torch.empty((n, sp.T), dtype=torch.uint8, device=eng.device) if "held" in has else None,
-                         instr=torch.empty((n, sp.V), dtype=torch.uint8, device=eng.device) if "instr" in has else None)
         for lo in range(0, n, eng.maxB):
             hi = min(n, lo + eng.maxB)
             B = hi - lo
             eng.stage_decoder_inputs(B, z=z[lo:hi], **{k: (None if v is None else np.asarray(v)[lo:hi]) for k, v in a.items()})
-            if sample is None and not want_vel and not all_heads:
-                eng.decode(B, want_probs=want_probs)
-            else:
-                spec = None
-                if sample is not None:
-                    spec = dict(sample, first_window=lo, uniforms={k: u[lo:hi] for k, u in (sample.get("uniforms") or {}).items()})
-                eng.decode(B, want_probs=want_probs, sample=spec, want_velocity=want_vel)
-            if want_probs:
-                outs.append(eng.outputs(B))
-            if describe is not None:       # behind the decode on this stream, outside the step plans; one read per engine batch
-                from . import descriptors
-                rows = eng._v("notes.argmax" if sample is None else "notes.choice", sp.T, eng.pad16(B))
-                idxs.append(descriptors.decoded_batch(rows, B, describe))
-                continue
-            if sweep is not None:          # likewise: the statistics kernel reads the decode's own buffers
-                from . import sweep as sweep_mod
-                kind, Bp = ".argmax" if sample is None else ".choice", eng.pad16(B)
-                idxs.append(sweep_mod.decoded_batch(eng._v("notes" + kind, sp.T, Bp), eng._v("out.vel_p", sp.T, Bp) if want_vel else None,
-                                                    eng._v("instr" + kind, sp.V, Bp) if "instr" in self._s.head_names() else None,
-                                                    B, sweep["p"], sweep.get("return_rolls", False)))
-                continue
-            if songs is not None:          # likewise: transposing device copies into the run's rolls, a song may straddle engine batches
-                kind, Bp = ".argmax" if sample is None else ".choice", eng.pad16(B)
-                songs["notes"][lo:hi].copy_(eng._v("notes" + kind, sp.T, Bp)[:, :B].t())
-                if songs["vel"] is not None:
-                    songs["vel"][lo:hi].copy_(eng._v("out.vel_p", sp.T, Bp)[:, :B].t())
-                if songs["held"] is not None:
-                    songs["held"][lo:hi].copy_(eng._v("held" + kind, sp.T, Bp)[:, :B].t())
-                if songs["instr"] is not None:
-                    songs["instr"][lo:hi].copy_(eng._v("instr" + kind, sp.V, Bp)[:, :B].t())
-                continue
-            if sample is None:
-                idxs.append(eng.note_indices(B))
-                if all_heads:
-                    heads.append(eng.argmax_indices(B))
-            else:
-                heads.append(eng.sampled_indices(B))
-                idxs.append(heads[-1]["notes"])
-            if all_heads and sp.meta_velocity:
-                heads[-1]["velocity"] = eng.velocity(B)
+            spec = None
+            if sample is not None:
+                spec = dict(sample, first_window=lo, uniforms={k: u[lo:hi] for k, u in (sample.get("uniforms") or {}).items()})
+            eng.decode(B, want_probs=sink.want_probs, sample=spec, want_velocity=sink.want_velocity and self._s.spec.meta_velocity)
+            sink.batch(eng, lo, hi, eng.decoded(B, sample is not None))
         eng.check_pipeline()
-        if describe is not None or sweep is not None:
-            return outs, idxs
-        if songs is not None:
-            return outs, None
-        notes = np.concatenate(idxs, 0) if idxs else np.zeros((0, sp.T), np.uint8)
-        if not all_heads:
-            return outs, notes
-        return outs, notes, ({k: np.concatenate([h[k] for h in heads], 0) for k in heads[0]} if heads else {})
+        return sink.result()
 
     def predict(self, x, batch_size=32, verbose=0):
-        outs, _ = self._run(x, batch_size)
+        outs = self._run(x, batch_size, sinks.Probabilities())
         res = [np.concatenate([o[h] for o in outs], 0) for h in self._s.head_names()]
         return res if len(res) > 1 else res[0]
 
     # ---- 'choice' decode on the device ---------------------------------------------------------------------
     sample_settings = None      # where temperature / number_of_tries / cutoff_sample_threshold come from (a settings module, namespace
                                 # or dict, read like packers._g does); None = the defaults of config.build_settings()
+
+    def _settings(self):
+        if self.sample_settings is None:
+            from .config import build_settings
+            return build_settings()
+        return self.sample_settings
 
     def _sample_spec(self, n, sample_method, temperature, seed, uniforms, heads):
         """arguments of Engine.decode(sample=...) for ``n`` windows, or None for 'argmax'"""
@@ -577,10 +527,7 @@ class Decoder(_ModelView):
             return None
         if sample_method != "choice":
             raise ValueError("unknown sample_method %r" % (sample_method,))
-        s = self.sample_settings
-        if s is None:
-            from .config import build_settings
-            s = build_settings()
+        s = self._settings()
         tries = int(packers._g(s, "number_of_tries"))
         if not 1 <= tries <= sampling.MAX_TRIES:
             raise NotImplementedError("number_of_tries = %d: the device sampler draws 1..%d times per row" % (tries, sampling.MAX_TRIES))
@@ -608,6 +555,21 @@ class Decoder(_ModelView):
                 us[name] = u
         return dict(temperature=tau, cutoff=float(packers._g(s, "cutoff_sample_threshold")), tries=tries, seed=int(seed), uniforms=us)
 
+    def _analysis(self, module, *check_args):
+        """(settings, module.params(settings)) of an analysis of what is decoded: ``sample_settings`` (None: the defaults of
+        config.build_settings()), whose max_voices must be the model's; the module's refusals come before anything is decoded"""
+        s = self._settings()
+        p, sp = module.params(s), self._s.spec
+        if p["voices"] != sp.V:
+            raise ValueError("max_voices of the settings (%d) is not the model's (%d)" % (p["voices"], sp.V))
+        module._check(sp.T, p, *check_args)
+        return s, p
+
+    def _sampled_run(self, x, batch_size, sink, sample_method, temperature, seed, uniforms):
+        """_run with the sample arguments of a public method"""
+        n = np.asarray(self._unpack(x)["z"]).shape[0]
+        return self._run(x, batch_size, sink, self._sample_spec(n, sample_method, temperature, seed, uniforms, self._softmax_heads()))
+
     def _softmax_heads(self):
         sp = self._s.spec
         return {k: T for k, T in (("notes", sp.T), ("instr", sp.V), ("held", sp.T), ("next", sp.T)) if k in self._s.head_names()}
@@ -620,9 +582,7 @@ class Decoder(_ModelView):
         ``decoder.sample_settings``); ``uniforms`` (n, T) or (n, T, number_of_tries) in [0, 1): the caller's random numbers in the
         caller's order; else they are generated on the device from ``seed`` (None: drawn from a generator of this model, seeded
         by ``create(seed=...)``) - the result for a window depends on the seed and the window's index only."""
-        n = np.asarray(self._unpack(x)["z"]).shape[0]
-        sample = self._sample_spec(n, sample_method, temperature, seed, uniforms, self._softmax_heads())
-        return self._run(x, batch_size, want_probs=False, sample=sample)[1]
+        return self._sampled_run(x, batch_size, sinks.NoteIndices(T=self._s.spec.T), sample_method, temperature, seed, uniforms)
 
     def predict_descriptors(self, x, batch_size=32, sample_method="argmax", temperature=None, seed=None, uniforms=None):
         """predict_note_indices plus the window descriptors of what was decoded: dict ``notes`` (n, T) uint8, ``signature`` (n, 15)
@@ -631,21 +591,8 @@ class Decoder(_ModelView):
         device-to-host read per engine batch brings all three.  Pitch range, silent column and segment length come from
         ``decoder.sample_settings`` (None: the defaults of config.build_settings()); arguments as predict_note_indices."""
         from . import descriptors
-        s = self.sample_settings
-        if s is None:
-            from .config import build_settings
-            s = build_settings()
-        p, sp = descriptors.params(s), self._s.spec
-        if p["voices"] != sp.V:
-            raise ValueError("max_voices of the settings (%d) is not the model's (%d)" % (p["voices"], sp.V))
-        descriptors._check(sp.T, p, True)
-        n = np.asarray(self._unpack(x)["z"]).shape[0]
-        sample = self._sample_spec(n, sample_method, temperature, seed, uniforms, self._softmax_heads())
-        parts = self._run(x, batch_size, want_probs=False, sample=sample, describe=p)[1]
-        if not parts:
-            return dict(notes=np.zeros((0, sp.T), np.uint8), signature=np.zeros((0, descriptors.SIGNATURE_LENGTH)),
-                        harmonicity=np.zeros((0, sp.V, sp.V)))
-        return {k: np.concatenate([d[k] for d in parts], 0) for k in ("notes", "signature", "harmonicity")}
+        _, p = self._analysis(descriptors, True)
+        return self._sampled_run(x, batch_size, sinks.Descriptors(p=p, T=self._s.spec.T), sample_method, temperature, seed, uniforms)
 
     def sweep_inputs(self, z, values, s):
         """the decoder inputs of the n * Z * K windows of a latent sweep, in the order (sample, dimension, value): window (i, d, k)
@@ -677,35 +624,26 @@ class Decoder(_ModelView):
         also ``notes`` (n, Z, K, T) uint8 and ``velocity`` (n, Z, K, T) float32 after the rules."""
         from . import packers
         from . import sweep as sweep_mod
-        s = self.sample_settings
-        if s is None:
-            from .config import build_settings
-            s = build_settings()
-        p, sp = sweep_mod.params(s), self._s.spec
-        if p["voices"] != sp.V:
-            raise ValueError("max_voices of the settings (%d) is not the model's (%d)" % (p["voices"], sp.V))
-        sweep_mod._check(sp.T, p)
+        (s, p), sp = self._analysis(sweep_mod), self._s.spec
         values = np.asarray(sweep_mod.sweep_values(range_end_in_stds, sigma, evaluations_per_dimension, positive_and_negative))
         z = np.asarray(z, np.float64)
         x = self.sweep_inputs(z, values, s)
         n, Z, K = z.shape[0], sp.Z, len(values)
         if n == 0:
             raise ValueError("z holds no sample")
-        N = n * Z * K
-        sample = self._sample_spec(N, sample_method, temperature, seed, None, self._softmax_heads())
-        parts = self._run(x, batch_size, want_probs=False, sample=sample, sweep=dict(p=p, return_rolls=return_rolls))[1]
-        table = np.concatenate([d["table"] for d in parts], 0).reshape(n, Z, K, sweep_mod.N_COLUMNS)
-        if parts and parts[0]["instr"] is not None:
-            programs = sweep_mod.programs_of(np.concatenate([d["instr"] for d in parts], 0),
-                                             packers._g(s, "instrument_attach_method")).reshape(n, Z, K, sp.V)
+        got = self._sampled_run(x, batch_size, sinks.SweepStatistics(p=p, T=sp.T, return_rolls=return_rolls), sample_method, temperature,
+                                seed, None)
+        table = got["table"].reshape(n, Z, K, sweep_mod.N_COLUMNS)
+        if got["instr"] is not None:
+            programs = sweep_mod.programs_of(got["instr"], packers._g(s, "instrument_attach_method")).reshape(n, Z, K, sp.V)
         else:          # the reference's default I: all piano
             programs = np.zeros((n, Z, K, sp.V), np.int64)
         summaries, infl, peaked, best = sweep_mod.summarize_sweep(table, programs)
         res = dict(table=table, programs=programs, values=values, summaries=summaries, influence=infl, most_peaked=peaked,
                    overall_best=best)
         if return_rolls:
-            res["notes"] = np.concatenate([d["notes"] for d in parts], 0).reshape(n, Z, K, sp.T)
-            res["velocity"] = np.concatenate([d["velocity"] for d in parts], 0).reshape(n, Z, K, sp.T)
+            res["notes"] = got["notes"].reshape(n, Z, K, sp.T)
+            res["velocity"] = got["velocity"].reshape(n, Z, K, sp.T)
         return res
 
     def predict_songs(self, xs, batch_size=32, sample_method="argmax", temperature=None, seed=None, uniforms=None, originals=None):
@@ -725,16 +663,9 @@ class Decoder(_ModelView):
         import torch
         from . import packers
         from . import reconstruction as rec
-        from .descriptors import _as_rolls
-        s = self.sample_settings
-        if s is None:
-            from .config import build_settings
-            s = build_settings()
+        from .rolls import as_rolls
+        (s, p), sp = self._analysis(rec), self._s.spec
         packers.refuse_meta_without_instrument(s)
-        p, sp = rec.params(s), self._s.spec
-        if p["voices"] != sp.V:
-            raise ValueError("max_voices of the settings (%d) is not the model's (%d)" % (p["voices"], sp.V))
-        rec._check(sp.T, p)
         xs = [_as_list(x) for x in xs]
         if not xs:
             return []
@@ -746,7 +677,7 @@ class Decoder(_ModelView):
                 raise ValueError("predict_songs: song %d has no windows - leave empty songs out of the list" % i)
         orig = None
         if originals is not None:
-            originals = [np.asarray(_as_rolls(o)) for o in originals]
+            originals = [np.asarray(as_rolls(o)) for o in originals]
             if len(originals) != len(xs):
                 raise ValueError("predict_songs: %d originals for %d songs" % (len(originals), len(xs)))
             for i, (o, m) in enumerate(zip(originals, lengths)):
@@ -755,17 +686,15 @@ class Decoder(_ModelView):
             orig = np.concatenate(originals, 0)
         x = [np.concatenate([np.asarray(xi[k]) for xi in xs], 0) for k in range(len(xs[0]))]
         n = int(sum(lengths))
-        sample = self._sample_spec(n, sample_method, temperature, seed, uniforms, self._softmax_heads())
-        rolls = {}
-        self._run(x, batch_size, want_probs=False, sample=sample, songs=rolls)
+        rolls = self._sampled_run(x, batch_size, sinks.SongRolls(n), sample_method, temperature, seed, uniforms)
         dev = rolls["notes"].device
         with torch.cuda.device(dev):
             first = torch.from_numpy(rec.first_windows(lengths, n)).to(dev)
-            outs = rec.run_on_device(rolls["notes"], rolls["vel"], rolls["held"], None if orig is None else torch.from_numpy(orig).to(dev),
+            outs = rec.run_on_device(rolls["notes"], rolls.get("velocity"), rolls.get("held"), None if orig is None else torch.from_numpy(orig).to(dev),
                                      first, p)
             velocity, starts, counts = (t.cpu().numpy() for t in outs)
             notes = rolls["notes"].cpu().numpy()
-            instr = None if rolls["instr"] is None else rolls["instr"].cpu().numpy()
+            instr = rolls["instr"].cpu().numpy() if "instr" in rolls else None
         metrics = rec.song_metrics(counts, lengths, sp.T, s) if orig is not None else None
         res, lo = [], 0
         for i, m in enumerate(lengths):
@@ -782,9 +711,7 @@ class Decoder(_ModelView):
         """The decoded index of EVERY softmax head - dict 'notes' (n, T), 'instr' (n, max_voices), 'held' (n, T), 'next' (n, T)
         uint8, as far as the model has them - plus 'velocity' (n, T) float32: what packers.process_decoder_indices needs, without
         a probability tensor reaching the host.  Arguments as predict_note_indices; ``uniforms``: dict head -> array."""
-        n = np.asarray(self._unpack(x)["z"]).shape[0]
-        sample = self._sample_spec(n, sample_method, temperature, seed, uniforms, self._softmax_heads())
-        return self._run(x, batch_size, want_probs=False, sample=sample, all_heads=True)[2]
+        return self._sampled_run(x, batch_size, sinks.AllIndices(), sample_method, temperature, seed, uniforms)
 
 
 class Autoencoder(_ModelView):

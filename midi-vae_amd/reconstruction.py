@@ -7,13 +7,8 @@ lane waits for another workgroup) or, with ``device=False``, through the NumPy m
 the yardstick of the device tests.  Both are pinned to the reference's own functions by tests/golden/recon.npz.  ``song_metrics`` and
 ``mean_metrics`` are host arithmetic on eight integers per window.
 
-The closed form.  Row t of a window is voice t % V of tick t // V; an index sounds unless it is the silent index, 255, or >= n_pitch.
-v0 of a row is its float32 velocity, 0 if the row does not sound.  Per voice, over the rows of the SONG: previous_pitch is the index
-of the voice's previous row (-1 if that row does not sound, or at the song's first tick); previous_velocity is v0 of the nearest
-earlier row for which ``v0 < threshold`` is false, 0.0 if there is none.  The result is previous_velocity if v0 < threshold, the row
-sounds, previous_pitch > 0 (not >= 0: the reference's own test) and previous_pitch != the row's index; 0 if v0 < threshold is false
-and the row does not sound; v0 otherwise.  Every output is an input value or a zero and every count an integer: device, mirror and
-reference are BIT-EQUAL.
+The rule is applied in its closed form (rolls.carried_velocity_rule states it).  Every output is an input value or a zero and every
+count an integer: device, mirror and reference are BIT-EQUAL.
 
 ``s`` is a settings mapping or module read like packers._g does: max_voices, low_crop, high_crop, include_silent_note,
 velocity_threshold_such_that_it_is_a_played_note, override_sampled_pitches_based_on_velocity_info (and, for ``song_metrics``,
@@ -22,13 +17,12 @@ meta_held_notes and meta_velocity).
 from __future__ import annotations
 
 import ctypes as C
-import math
 
 import numpy as np
 
 from . import hiplib as hl
-from .descriptors import _as_rolls, _sounding
 from .packers import _g
+from .rolls import as_rolls, base_params, carried_velocity_rule, check_rows, device_roll, host_roll, sounding
 
 COUNTS = ("original_notes", "predicted_notes", "correct_notes", "not_predicted_notes", "new_predicted_notes", "note_starts",
           "note_starts_on_silent_prediction", "note_starts_on_silent_original")
@@ -41,22 +35,14 @@ METRICS = ("total_original_notes", "total_predicted_notes", "pitch_reconstructio
 
 def params(s):
     """what the song-level decode reads from the settings"""
-    n_pitch = int(_g(s, "high_crop")) - int(_g(s, "low_crop"))
-    return dict(voices=int(_g(s, "max_voices")), n_pitch=n_pitch, silent=n_pitch if _g(s, "include_silent_note") else -1,
-                threshold=float(_g(s, "velocity_threshold_such_that_it_is_a_played_note")),
+    return dict(base_params(s), threshold=float(_g(s, "velocity_threshold_such_that_it_is_a_played_note")),
                 override=bool(_g(s, "override_sampled_pitches_based_on_velocity_info")))
 
 
 def _check(T, p):
-    V = p["voices"]
-    if not 2 <= V <= 8 or T % V:
-        raise ValueError("rows per window (%d) must be a multiple of max_voices (%d, 2..8)" % (T, V))
-    if T > MAX_T:
-        raise ValueError("rows per window (%d) above the limit of the song-level decode (%d)" % (T, MAX_T))
+    check_rows(T, p, MAX_T, "song-level decode")
     if not 1 <= p["n_pitch"] <= 192:
         raise ValueError("%d pitch columns: the song-level decode takes 1..192" % p["n_pitch"])
-    if not math.isfinite(p["threshold"]):
-        raise ValueError("the velocity threshold must be finite")
 
 
 def first_windows(lengths, n):
@@ -77,33 +63,14 @@ def default_velocity(p):
 # ---- the NumPy mirror ----------------------------------------------------------------------------------------------------------
 def _mirror(idx, vel, held, orig, first, p):
     n, T = idx.shape
-    V, thr = p["voices"], p["threshold"]
-    ticks = T // V
-    on = _sounding(idx, p)
+    thr = p["threshold"]
+    on = sounding(idx, p)
     if vel is None:
         velocity = np.full((n, T), default_velocity(p), np.float32)
     else:
-        v0 = np.where(on, vel, np.float32(0)).astype(np.float32)
-        velocity = v0
-        if p["override"] and n:
-            # one sequence per voice through all songs: row i of (L, V) is tick i % ticks of window i // ticks
-            L = n * ticks
-            seq = v0.reshape(L, V)
-            snd = on.reshape(L, V)
-            pitch = np.where(snd, idx.reshape(L, V).astype(np.int64), -1)
-            song_row0 = np.repeat(first.astype(np.int64) * ticks, ticks)          # the first row of the row's song
-            at = np.arange(L)
-            previous_pitch = np.full((L, V), -1, np.int64)
-            previous_pitch[1:] = pitch[:-1]
-            previous_pitch[at == song_row0] = -1
-            loud = ~(seq.astype(np.float64) < thr)                                # "velocity is silent" is false
-            last = np.maximum.accumulate(np.where(loud, at[:, None], -1), axis=0)
-            before = np.full((L, V), -1, np.int64)                                # the nearest earlier loud row
-            before[1:] = last[:-1]
-            inside = before >= song_row0[:, None]
-            previous_velocity = np.where(inside, np.take_along_axis(seq, np.maximum(before, 0), axis=0), np.float32(0))
-            inherit = ~loud & snd & (previous_pitch > 0) & (previous_pitch != pitch)
-            velocity = np.where(inherit, previous_velocity, np.where(loud & ~snd, np.float32(0), seq)).astype(np.float32).reshape(n, T)
+        velocity = np.where(on, vel, np.float32(0)).astype(np.float32)
+        if p["override"]:
+            velocity = carried_velocity_rule(idx, on, velocity, first, p)
     if held is not None:
         starts = held.astype(np.uint8)
     elif vel is not None:
@@ -116,7 +83,7 @@ def _mirror(idx, vel, held, orig, first, p):
     counts[:, 5] = is_start.sum(1)
     counts[:, 6] = (is_start & ~on).sum(1)
     if orig is not None:
-        orig_on = _sounding(orig, p)
+        orig_on = sounding(orig, p)
         counts[:, 0] = orig_on.sum(1)
         counts[:, 2] = (orig_on & on & (orig == idx)).sum(1)
         counts[:, 7] = (is_start & ~orig_on).sum(1)
@@ -168,32 +135,6 @@ def run_on_device(idx, vel, held, orig, first, p):
     return vel_out, start_out, counts
 
 
-def _device_tensor(a, dtype, what, shape=None, device=None):
-    """a 2-D device tensor of ``dtype``: ``a`` itself if it is one (any strides), else the host array uploaded"""
-    import torch
-    if hasattr(a, "data_ptr"):
-        if a.dtype != dtype or a.dim() != 2 or not a.is_cuda:
-            raise ValueError("device %s are a 2-D %s tensor (n, T), any strides" % (what, str(dtype).replace("torch.", "")))
-        t = a
-    else:
-        a = _as_rolls(a) if dtype == torch.uint8 else np.ascontiguousarray(a, np.float32)
-        t = torch.from_numpy(np.ascontiguousarray(a)).to(device or "cuda")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError("%s have shape %r, the notes %r" % (what, tuple(t.shape), tuple(shape)))
-    return t
-
-
-def _host_array(a, kind, what, shape=None):
-    if a is None:
-        return None
-    if hasattr(a, "data_ptr"):
-        a = a.cpu().numpy()
-    a = _as_rolls(a) if kind == "u8" else np.asarray(a).astype(np.float32)
-    if shape is not None and a.shape != shape:
-        raise ValueError("%s have shape %r, the notes %r" % (what, a.shape, shape))
-    return a
-
-
 def song_decode(idx, vel, lengths, s, held=None, orig=None, device=True):
     """The song-level decode of ``n`` windows that form ``len(lengths)`` songs (``lengths``: the songs' window counts, in order; their
     sum is n and each is > 0, else ValueError).  ``idx`` (n, T) uint8 index rolls or (n, T, K) one-hot rolls, ``vel`` (n, T) float
@@ -205,28 +146,28 @@ def song_decode(idx, vel, lengths, s, held=None, orig=None, device=True):
     if device:
         import torch
         if not hasattr(idx, "data_ptr"):
-            idx = _as_rolls(idx)
+            idx = as_rolls(idx)
         if len(idx.shape) != 2:
             raise ValueError("notes are (n, T) index rolls, got shape %r" % (tuple(idx.shape),))
         n, T = idx.shape
         _check(T, p)
         first = first_windows(lengths, n)          # (every refusal comes before anything touches the device)
-        t = _device_tensor(idx, torch.uint8, "notes")
-        v = None if vel is None else _device_tensor(vel, torch.float32, "velocities", t.shape, t.device)
-        h = None if held is None else _device_tensor(held, torch.uint8, "held notes", t.shape, t.device)
-        o = None if orig is None else _device_tensor(orig, torch.uint8, "originals", t.shape, t.device)
+        t = device_roll(idx, torch.uint8, "notes")
+        v = device_roll(vel, torch.float32, "velocities", t.shape, device=t.device)
+        h = device_roll(held, torch.uint8, "held notes", t.shape, device=t.device)
+        o = device_roll(orig, torch.uint8, "originals", t.shape, device=t.device)
         if n == 0:
             return dict(velocity=np.zeros((0, T), np.float32), starts=np.zeros((0, T), np.uint8), counts=np.zeros((0, N_COUNTS), np.int32))
         with torch.cuda.device(t.device):
             outs = run_on_device(t, v, h, o, torch.from_numpy(first).to(t.device), p)
         velocity, starts, counts = (x.cpu().numpy() for x in outs)
     else:
-        a = _host_array(idx, "u8", "notes")
+        a = host_roll(idx, np.uint8, "notes")
         n, T = a.shape
         _check(T, p)
         first = first_windows(lengths, n)
-        velocity, starts, counts = _mirror(a, _host_array(vel, "f32", "velocities", a.shape), _host_array(held, "u8", "held notes", a.shape),
-                                           _host_array(orig, "u8", "originals", a.shape), first, p)
+        velocity, starts, counts = _mirror(a, host_roll(vel, np.float32, "velocities", a.shape), host_roll(held, np.uint8, "held notes", a.shape),
+                                           host_roll(orig, np.uint8, "originals", a.shape), first, p)
     return dict(velocity=velocity, starts=starts, counts=counts)
 
 

@@ -28,8 +28,8 @@ import warnings
 import numpy as np
 
 from . import hiplib as hl
-from .descriptors import _as_rolls, _sounding
 from .packers import _g
+from .rolls import HostPack, as_rolls, base_params, carried_velocity_rule, check_rows, device_roll, host_roll, sounding
 
 _SIX = ("mean", "median", "min", "max", "range", "std")
 COUNTED = (35, 39)          # the reference's two "specific pitch" columns
@@ -41,21 +41,13 @@ MAX_T = 65536
 
 def params(s, counted=COUNTED):
     """what the statistics read from the settings"""
-    n_pitch = int(_g(s, "high_crop")) - int(_g(s, "low_crop"))
     thr = float(_g(s, "velocity_threshold_such_that_it_is_a_played_note"))
-    return dict(voices=int(_g(s, "max_voices")), n_pitch=n_pitch, silent=n_pitch if _g(s, "include_silent_note") else -1,
-                threshold=thr, default_velocity=thr + (1. - thr) * 0.5,
+    return dict(base_params(s), threshold=thr, default_velocity=thr + (1. - thr) * 0.5,
                 override=bool(_g(s, "override_sampled_pitches_based_on_velocity_info")), count_a=int(counted[0]), count_b=int(counted[1]))
 
 
 def _check(T, p):
-    V = p["voices"]
-    if not 2 <= V <= 8 or T % V:
-        raise ValueError("rows per window (%d) must be a multiple of max_voices (%d, 2..8)" % (T, V))
-    if T > MAX_T:
-        raise ValueError("rows per window (%d) above the limit of the statistics (%d)" % (T, MAX_T))
-    if not math.isfinite(p["threshold"]):
-        raise ValueError("the velocity threshold must be finite")
+    check_rows(T, p, MAX_T, "statistics")
 
 
 # ---- the NumPy mirror ----------------------------------------------------------------------------------------------------------
@@ -88,47 +80,27 @@ def _velocity_stats(values):
     return [mean, _median(values), min(values), max(values), max(values) - min(values), math.sqrt(dev / float(len(values)))]
 
 
-def velocity_rules(idx, on, vel, p):
-    """the post-rule velocities of ONE window as a list of Python floats: ``idx`` / ``on`` / ``vel`` lists of T indices, sounding
-    flags and head values (``vel`` None: the default velocity everywhere, nothing zeroed, no rule)"""
-    T, V, thr = len(idx), p["voices"], p["threshold"]
-    if vel is None:
-        return [p["default_velocity"]] * T
-    raw = [float(v) if o else 0.0 for v, o in zip(vel, on)]
-    out = list(raw)
-    if not p["override"]:
-        return out
-    for voice in range(V):
-        previous_pitch, previous_velocity = -1, 0.0
-        for t in range(voice, T, V):
-            pitch = idx[t] if on[t] else -1
-            velocity_is_silent = raw[t] < thr
-            if velocity_is_silent:
-                if on[t] and previous_pitch > 0 and previous_pitch != pitch:          # (> 0, not >= 0: the reference's own test)
-                    out[t] = previous_velocity
-            elif not on[t]:
-                out[t] = 0.0
-            previous_pitch = pitch
-            if not velocity_is_silent:
-                previous_velocity = raw[t]                                            # (the value before the rule)
-    return out
-
-
 def _mirror(idx, vel, p):
     n, T = idx.shape
     V = p["voices"]
-    on = _sounding(idx, p)
+    on = sounding(idx, p)
+    if vel is None:          # no velocity head: the default velocity everywhere (a double), nothing zeroed, no rule
+        after = [[p["default_velocity"]] * T] * n
+    else:
+        v0 = np.where(on, vel, np.float32(0)).astype(np.float32)
+        if p["override"]:          # every window its own song
+            v0 = carried_velocity_rule(idx, on, v0, np.arange(n), p)
+        after = v0.astype(np.float64).tolist()          # Python floats from here on: `> threshold` must compare doubles
     table = np.full((n, N_COLUMNS), np.nan)
     roll = np.zeros((n, T), np.float32)
     for w in range(n):
-        xs, os_ = idx[w].tolist(), on[w].tolist()
+        xs, os_, out = idx[w].tolist(), on[w].tolist(), after[w]
         pitches, in_a, in_b = [], 0, 0
         for k in range(0, T, V):
             notes = sorted({x for x, o in zip(xs[k:k + V], os_[k:k + V]) if o})
             pitches.extend(notes)
             in_a += p["count_a"] in notes
             in_b += p["count_b"] in notes
-        out = velocity_rules(xs, os_, None if vel is None else vel[w].tolist(), p)
         roll[w] = out
         starts = [t for t in range(T) if out[t] > p["threshold"]]
         table[w] = ([float(len(pitches))] + _integer_stats(pitches) + [float(in_a), float(in_b), float(len(starts))] +
@@ -149,26 +121,10 @@ def enqueue(idx_ptr, vel_ptr, stride_t, stride_w, n, T, p, stats_out, vel_out, s
 
 def _device_run(idx, vel, p, want_velocity, device=None):
     import torch
-    if hasattr(idx, "data_ptr"):
-        t = idx
-        if t.dtype != torch.uint8 or t.dim() != 2 or not t.is_cuda:
-            raise ValueError("a device roll is a 2-D uint8 tensor (n, T), any strides")
-    else:
-        t = torch.from_numpy(np.ascontiguousarray(idx)).to(device or "cuda")
+    t = device_roll(idx, torch.uint8, "notes", device=device)
     n, T = t.shape
     _check(T, p)
-    v = None
-    if vel is not None:
-        if hasattr(vel, "data_ptr"):
-            v = vel
-            if v.dtype != torch.float32 or v.shape != t.shape or v.stride() != t.stride() or v.device != t.device:
-                raise ValueError("device velocities are a float32 tensor with the shape and strides of the notes")
-        else:
-            vel = np.asarray(vel)
-            if vel.shape != (n, T):
-                raise ValueError("velocities have shape %r, the notes %r" % (vel.shape, (n, T)))
-            v = torch.empty_strided(t.shape, t.stride(), dtype=torch.float32, device=t.device)
-            v.copy_(torch.from_numpy(np.ascontiguousarray(vel, np.float32)).to(t.device))
+    v = device_roll(vel, torch.float32, "velocities", t.shape, strides_of=t)
     stats = torch.empty((n, N_COLUMNS), dtype=torch.float64, device=t.device)
     roll = torch.empty((n, T), dtype=torch.float32, device=t.device) if want_velocity else None
     if n:
@@ -185,29 +141,22 @@ def decoded_batch(rows, vel, instr, B, p, return_rolls=False):
     post-rule velocities ride along).  dict ``table`` (B, 22) float64, ``instr`` (B, V) uint8 or None, and with ``return_rolls``
     ``notes`` (B, T) uint8 and ``velocity`` (B, T) float32."""
     import torch
-    T, Bp = rows.shape
-    V = p["voices"]
-    nb_tab = B * N_COLUMNS * 8
-    nb_roll = B * T * 4 if return_rolls else 0
-    nb_instr = B * V if instr is not None else 0
-    nb_notes = B * T if return_rolls else 0
-    pack = torch.empty(nb_tab + nb_roll + nb_instr + nb_notes, dtype=torch.uint8, device=rows.device)
-    table = pack[:nb_tab].view(torch.float64).view(B, N_COLUMNS)
-    roll = pack[nb_tab:nb_tab + nb_roll].view(torch.float32).view(B, T) if return_rolls else None
-    with torch.cuda.device(rows.device):
-        enqueue(rows.data_ptr(), None if vel is None else vel.data_ptr(), rows.stride(0), rows.stride(1), B, T, p, table, roll,
-                torch.cuda.current_stream().cuda_stream)
-        at = nb_tab + nb_roll
-        if instr is not None:
-            pack[at:at + nb_instr].view(B, V).copy_(instr[:, :B].t())
-        if return_rolls:
-            pack[at + nb_instr:].view(B, T).copy_(rows[:, :B].t())
-        host = pack.cpu().numpy()
-    res = dict(table=host[:nb_tab].view(np.float64).reshape(B, N_COLUMNS).copy(),
-               instr=host[at:at + nb_instr].reshape(B, V).copy() if instr is not None else None)
+    T, V = rows.shape[0], p["voices"]
+    blocks = [("table", torch.float64, (B, N_COLUMNS))]
+    if instr is not None:
+        blocks.append(("instr", torch.uint8, (B, V)))
     if return_rolls:
-        res["velocity"] = host[nb_tab:at].view(np.float32).reshape(B, T).copy()
-        res["notes"] = host[at + nb_instr:].reshape(B, T).copy()
+        blocks += [("velocity", torch.float32, (B, T)), ("notes", torch.uint8, (B, T))]
+    pack = HostPack(rows.device, blocks)
+    with torch.cuda.device(rows.device):
+        enqueue(rows.data_ptr(), None if vel is None else vel.data_ptr(), rows.stride(0), rows.stride(1), B, T, p, pack.views["table"],
+                pack.views.get("velocity"), torch.cuda.current_stream().cuda_stream)
+        if instr is not None:
+            pack.views["instr"].copy_(instr[:, :B].t())
+        if return_rolls:
+            pack.views["notes"].copy_(rows[:, :B].t())
+        res = pack.to_host()
+    res.setdefault("instr", None)
     return res
 
 
@@ -215,17 +164,12 @@ def window_statistics(notes, velocity, s, device=True, return_velocity=False, co
     """(n, 22) float64 table (columns: ``COLUMNS``) of (n, T) uint8 index rolls, (n, T, K) one-hot rolls or a 2-D uint8 device tensor
     and their (n, T) velocities - a float array, a float32 device tensor with the strides of ``notes``, or None for a model
     without the velocity head.  ``return_velocity``: (table, (n, T) float32 velocities after the rules)."""
-    p, idx = params(s, counted), _as_rolls(notes)
+    p, idx = params(s, counted), as_rolls(notes)
     if device:
         table, roll = _device_run(idx, velocity, p, return_velocity)
     else:
-        if hasattr(idx, "data_ptr"):
-            idx = idx.cpu().numpy()
-        if velocity is not None:
-            velocity = velocity.cpu().numpy() if hasattr(velocity, "data_ptr") else np.asarray(velocity)
-            if velocity.shape != idx.shape:
-                raise ValueError("velocities have shape %r, the notes %r" % (velocity.shape, idx.shape))
-            velocity = velocity.astype(np.float32)
+        idx = host_roll(idx, np.uint8, "notes")
+        velocity = host_roll(velocity, np.float32, "velocities", idx.shape)
         _check(idx.shape[1], p)
         table, roll = _mirror(idx, velocity, p)
     return (table, roll) if return_velocity else table

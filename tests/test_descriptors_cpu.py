@@ -21,6 +21,7 @@ import torch
 import midi_vae_amd  # noqa: F401
 from midi_vae_amd import descriptors as de
 from midi_vae_amd import hiplib as hl
+from midi_vae_amd import rolls
 from tests import descriptor_contract as dc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -78,7 +79,7 @@ def test_fixture_exercises_the_quirks(fx):
     off = ~np.eye(4, dtype=bool)
     share = np.isnan(fx["harmonicity"][:, off]).mean()
     assert 0.05 <= share <= 0.60, share
-    on = de._sounding(fx["idx"], de.params(fx["s"])).reshape(258, 16, 4)
+    on = rolls.sounding(fx["idx"], de.params(fx["s"])).reshape(258, 16, 4)
     counts = np.array([[len(set(fx["idx"][w].reshape(16, 4)[k][on[w, k]])) for k in range(16)] for w in range(258)])
     assert np.any((counts[:, 1:] != counts[:, :-1]) & (counts[:, 1:] > 0) & (counts[:, :-1] > 0))
     assert np.all(fx["signature"][256] == 0) and np.all(np.isnan(fx["harmonicity"][256][off]))

@@ -20,6 +20,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import midi_vae_amd  # noqa: E402,F401
 from midi_vae_amd import packers as pk  # noqa: E402
+from midi_vae_amd import rolls  # noqa: E402
 from midi_vae_amd import sweep as sw  # noqa: E402
 from midi_vae_amd.config import build_settings, create_kwargs  # noqa: E402
 
@@ -48,7 +49,7 @@ def host_route(dec, dec_in, s, shape):
         vel[w] = pk.process_decoder_indices(s, one)[2]
     p = sw.params(s)
     table = np.full((vel.shape[0], sw.N_COLUMNS), np.nan)
-    on = sw._sounding(ind["notes"], p)
+    on = rolls.sounding(ind["notes"], p)
     for w in range(vel.shape[0]):                   # the mirror's statistics on the post-rule velocities
         xs, os_, out = ind["notes"][w].tolist(), on[w].tolist(), vel[w].astype(np.float64).tolist()
         pitches = []
