@@ -27,7 +27,7 @@ def run(cell, lr, steps, dtype="bf16", B=16, T=512, every=10, seed=31, out=sys.s
     import midi_vae_amd  # noqa: F401
     from midi_vae_amd.engine import Engine
     from oracle.vae_oracle import OracleVAE, make_cfg
-    from tests.test_engine_gpu import _problem, _stage
+    from tests.loss_terms import problem as _problem, stage as _stage
     spec, params, batch, raw = _problem(cell, B, seed=seed, H=256, Z=64, T=T, epsilon_std=0.1)
     spec.lr = lr
     orc = OracleVAE(make_cfg(**spec.oracle_cfg()))

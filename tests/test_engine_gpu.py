@@ -13,48 +13,14 @@ from midi_vae_amd import ops
 from midi_vae_amd.engine import Engine
 from midi_vae_amd.layout import ModelSpec, init_params
 from oracle.vae_oracle import OracleVAE, make_cfg
+from tests import loss_terms as lt
 from tests import parity as par
 
 pytestmark = pytest.mark.gpu
 
 
-def _onehot(idx, n):
-    out = np.zeros(idx.shape + (n,))
-    np.put_along_axis(out, idx[..., None].astype(np.int64), 1, -1)
-    return out
-
-
-def _problem(cell, B, seed=0, H=64, Z=32, T=12, V=4, C=2, **kw):
-    spec = ModelSpec(cell=cell, H=H, Z=Z, T=T, V=V, C=C, lr=1e-3, **kw)
-    rng = np.random.default_rng(seed)
-    params = init_params(spec, seed)
-    for k in params:                       # non-zero biases so every path carries signal
-        if k.endswith(".b"):
-            params[k] = (rng.standard_normal(params[k].shape) * 0.1).astype(np.float32)
-    x_idx = np.where(rng.random((B, T)) < 0.35, spec.Dout - 1, rng.integers(0, spec.Dout - 1, (B, T))).astype(np.uint8)
-    i_idx = rng.integers(0, spec.ID, (B, V)).astype(np.uint8)
-    vel = np.where((x_idx == spec.Dout - 1) | (rng.random((B, T)) < 0.5), 0.0, 0.5 + 0.5 * rng.random((B, T)))
-    vel = vel.astype(np.float32)
-    hist = (rng.standard_normal((B, Z)) * 0.1).astype(np.float32)
-    eps = (rng.standard_normal((B, Z)) * spec.epsilon_std).astype(np.float32)
-    c_idx = rng.integers(0, C, (B,)).astype(np.uint8)
-    w_notes = np.where(x_idx == spec.Dout - 1, 0.5, 1.0)
-    d_idx = (rng.random((B, T)) < 0.4).astype(np.uint8)                   # held-notes roll (reference import_midi.py:267-286)
-    n_idx = rng.integers(0, spec.Dout, (B, T)).astype(np.uint8)          # the next window's notes
-    sig = (rng.standard_normal((B, spec.SD)) * 0.5).astype(np.float32)        # signature vectors (reference data_class.py:96-221)
-    add = rng.standard_normal((B, max(spec.add_dim, 1))).astype(np.float32)[:, :spec.add_dim]
-    batch = dict(X=_onehot(x_idx, spec.Din), I=_onehot(i_idx, spec.ID), Vel=vel[..., None].astype(np.float64),
-                 Hist=hist.astype(np.float64), Y=_onehot(x_idx, spec.Dout), C=_onehot(c_idx, C), w_notes=w_notes,
-                 Held=_onehot(d_idx, 2), Next=_onehot(n_idx, spec.Dout), S=sig.astype(np.float64), Add=add.astype(np.float64))
-    raw = dict(x_idx=x_idx, i_idx=i_idx, vel=vel, hist=hist, eps=eps, c_idx=c_idx, w_notes=w_notes, d_idx=d_idx, n_idx=n_idx,
-               sig=sig, add=add)
-    return spec, params, batch, raw
-
-
-def _stage(eng, raw, B):
-    eng.stage_encoder_inputs(raw["x_idx"], raw["i_idx"], raw["vel"], raw["eps"], d_idx=raw["d_idx"])
-    eng.stage_decoder_inputs(B, hist=raw["hist"], add=raw["add"])
-    eng.stage_targets(B, raw["x_idx"], raw["c_idx"], w_notes=raw["w_notes"], n_idx=raw["n_idx"], sig=raw["sig"])
+# the problem generator lives in tests/loss_terms.py (no test module is imported for its helpers): same seeds, same draws
+_onehot, _problem, _stage = lt.onehot, lt.problem, lt.stage
 
 
 def _rel_l2(a, b):
