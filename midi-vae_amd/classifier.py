@@ -98,7 +98,6 @@ class ClassifierEngine(Engine):
             self.scal.zero_()
         inp = (dict(idx=self._v("in.x_idx", s.T, B)) if s.xmode == "index" else dict(xs=self._v("in.x_val", s.T, B)))
         self._stack_forward(self.layers, B, h_last=self._v("h_last", B, s.H), h_last_ld=s.H, slot=0, **inp)
-        self._prefork = None
         top = self._v(self.layers[-1].prefix + ".hs", s.T + 1, B, s.H)[s.T]      # (B,H) in the compute dtype
         h = self.head["cls"]
         tg = self._have_targets
@@ -124,7 +123,6 @@ class ClassifierEngine(Engine):
             ops.colsum(dl, B, s.C, G["cls.out.b"], ldx=h.NP)
         inp = (dict(idx=self._v("in.x_idx", s.T, B)) if s.xmode == "index" else dict(xs=self._v("in.x_val", s.T, B)))
         self._stack_backward(self.layers, B, dh_last=dh, dh_last_ld=s.H, slot=3, **inp)
-        self._prefork = None
         self._join(self.s_grad)
         self._join(self.s_grad2)
 

@@ -16,6 +16,7 @@ from __future__ import annotations
 
 from collections import OrderedDict
 
+import contextlib
 import ctypes as C
 import numpy as np
 import os
@@ -35,6 +36,7 @@ from .engine_phases import PhaseLaunches
 from .engine_plan import PlannedSteps
 from .engine_grads import ParamGradients
 from .engine_steps import TrainSteps
+from .engine_schedule import CallState, PhaseState
 from .engine_buffers import Buffers, _Rec, _Head, _Aux        # noqa: F401  (the records of the layer description)
 from .slots import *        # noqa: F401,F403  (scalar slots S_*, N_SCALARS, X_EXT)
 from .slots import N_SCALARS, X_EXT, X_GATHER2
@@ -107,8 +109,7 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
                 self.s_grad2 = torch.cuda.Stream()      # second gradient stream: input-kernel / bias gradients
                 self.s_layer = [torch.cuda.Stream() for _ in range(nl)]
                 self.s_proj = [self._own_queue_stream() for _ in range(nl)]     # x*W / dX of pipelined stacks
-        self._prefork = None
-        self._branches_stay_forked = False
+        self._call, self._ph = CallState(), PhaseState()     # schedule state of the running call / recurrence phase (engine_schedule.py)
         self._bucket_hook = None         # data parallel: dp.BucketedAllReduce of the running train_step
         self.s_comm = None               # ... and the stream its early bucket starts on (created on first use)
         self.status_allreduce = None     # data parallel: MAX of the pipeline status word over the ranks (dp.DataParallel)
@@ -120,16 +121,6 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
         # Parameter-gradient GEMMs once per layer (after its BPTT), NOT per time chunk: throughput GEMMs running beside the
         # latency-bound recurrences slow those down by more than the tail they would save.
         self._grads_clean = False
-        self._deferred_gemms, self._deferred_small = None, []
-        # The decoder notes stack's weight gradients are a K-streaming launch too (_decoder_kstream_ok), the side heads' gradient
-        # GEMMs are held behind the latent chain beside it (_hold_side, armed in backward), and the dU GEMM of a full-length
-        # single-layer encoder branch joins the encoder's K-streaming launch (settled r02: LSTM 7.60 -> 7.50 ms, GRU 6.55 -> 6.38;
-        # profiles/r02_n_ab_kstream_gradients.txt)
-        self._hold_side = False
-        self._kstream_extra = None
-        self._grad_streams = None        # (s_grad, s_grad2) unless overridden for a phase
-        self._n_side = 0                 # recurrences running beside the stack being scheduled (residency, _pipelined)
-        self._cur_B = self.maxB          # padded batch of the call being scheduled
         self._pw = False                 # a per-window evaluation step in progress (eval_step(per_window=True))
         self._sample_mode, self._want_vel = None, False      # a 'choice' decode in progress (Engine.decode): (heads with supplied uniforms, tries)
         self.num_cus = torch.cuda.get_device_properties(self.device).multi_processor_count
@@ -141,17 +132,11 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
         # the recurrences of a phase as ONE launch on the critical queue instead of one launch per queue (engine_phases.py), up to
         # phase_max_B windows (knobs.py)
         self.phase_multi = True
-        self._last_stack_gate = None
-        self._top_publish = None
         # (_join; r03_z: -0.02 / -0.04 ms.  NOT when kernels are run one at a time - rocprofv3 counter collection: a critical queue parked
         #  in a value wait and a writer queue held back behind it never finish; event joins work there)
         serial = getattr(self, "_serial_queues", False) or (share is not None and getattr(share, "_serial_queues", False))
         self.value_join = not serial and len(self.s_proj) > 0     # (no stacked layer: no probe was run)
         self._join_seq = {}
-        self._grad_portion_jobs = None
-        self._single_slot, self._single_slot_end = 0, 3
-        self._after_chain = None
-        self._tail_streams = []          # queues besides the two gradient queues that carry gradient work of the running step
         if share is None:
             self.set_params(self._initial_params(seed))
         self._build_graph_description()
@@ -160,7 +145,6 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
         self._prep = None                # PrepBatch per (step count pending): prepare_weights
         self._zero_scal_job = None
         self._zero_grads_job = None
-        self._deferred_side = None       # (phase launches) side-queue work to be released by a device counter instead of an event
         self._xp0_bias = set()           # constant-input cells whose xp0 rows hold the bias (written by the last weight preparation)
         self.start_zero = {}             # layer prefix -> the staged start rows of its head are all zero (staging)
         self._count_only = None
@@ -269,26 +253,37 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
         """``streams`` wait for everything enqueued so far on the current one.  Forks and joins put ONE packet on the critical queue
         however many streams branch off or come back (settled in round 1 against one event and one wait per stream: 9.3 -> 8.86 ms
         per step)"""
-        if self._prefork is not None and self._prefork[0] == torch.cuda.current_stream() and \
-                all(any(st is p for p in self._prefork[1]) for st in streams):
+        prefork = self._ph.prefork
+        if prefork is not None and prefork[0] == torch.cuda.current_stream() and \
+                all(any(st is p for p in prefork[1]) for st in streams):
             for st in streams:              # already forked by _fork_with_stack
-                self._prefork[1].remove(st)
+                prefork[1].remove(st)
             return
         if streams:
             ev = self._ev_record(torch.cuda.current_stream())       # ONE marker packet on this queue, however many streams branch off
             for st in streams:
                 self._ev_wait(st, ev)
 
-    def _fork_with_stack(self, layers, *streams, also=()):
-        """fork ``streams`` AND the streams a pipelined stack over ``layers`` will use (and ``also``) with one event; the
-        forks the callees then ask for from THIS stream for those streams are skipped, once each (nothing they depend on
-        may be launched on the current stream in between; the caller clears ``_prefork`` after the stack)."""
+    def _fork_with_stack(self, layers, B, *streams, also=()):
+        """fork ``streams`` AND the streams a pipelined stack over ``layers`` will use at a padded batch of B (and ``also``)
+        with one event; the forks the callees then ask for from THIS stream for those streams are skipped, once each (nothing
+        they depend on may be launched on the current stream in between; the note ends with the phase: PhaseState.prefork)."""
         extra = ()
-        if self._pipelined(layers):
+        if self._pipelined(layers, B):
             L = len(layers)
             extra = (*self.s_layer[:L - 1], *self.s_proj[:L - 1], *also)
         self._fork(*streams, *extra)
-        self._prefork = (torch.cuda.current_stream(), list(extra)) if extra else None
+        self._ph.prefork = (torch.cuda.current_stream(), list(extra)) if extra else None
+
+    @contextlib.contextmanager
+    def _scheduling(self, attr, state):
+        """``state`` (engine_schedule.py) is the engine's ``attr`` - ``_call`` or ``_ph`` - for the duration of the block; a
+        fresh default instance takes its place where the block ends, however it ends"""
+        setattr(self, attr, state)
+        try:
+            yield state
+        finally:
+            setattr(self, attr, type(state)())
 
     def _join(self, *streams, word=None):
         """the current stream waits for ``streams``.  ``word`` (an index into the engine's join words; ``value_join``): the last
@@ -327,11 +322,11 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
 
     def _side(self, fn):
         """Run ``fn`` (parameter-gradient work nobody waits for before the optimizer) on the second gradient stream,
-        ordered after everything enqueued so far on the current stream.  While a list is collecting (``_deferred_side``: the
+        ordered after everything enqueued so far on the current stream.  While a list is collecting (``CallState.deferred_side``: the
         phase launch that follows releases the work by a device counter - an event record here is one more packet, ~30 us, on
         the critical queue) the work is only noted."""
-        if self._deferred_side is not None:
-            self._deferred_side.append(fn)
+        if self._call.deferred_side is not None:
+            self._call.deferred_side.append(fn)
             return
         self._wait_stream(self.s_grad2, torch.cuda.current_stream())
         with torch.cuda.stream(self.s_grad2):
@@ -541,18 +536,18 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
                  **chunked)
 
     # ---- time-pipelined stacks (slot-interleaved LSTM kernels) ---------------------------------------------------
-    def _resident_cus(self, layers, B, backward=None, side=False):
+    def _resident_cus(self, layers, B, backward=None, n_side=0):
         """CUs the kernels of a time-pipelined stack over ``layers`` occupy AT THE SAME TIME at a padded batch of B windows
-        (``side``: plus the ``_n_side`` single-layer recurrences of the phase running beside it).  A recurrent workgroup (16
+        (plus the ``n_side`` single-layer recurrences of the phase running beside it).  A recurrent workgroup (16
         windows) owns a whole CU (__launch_bounds__(256, 1): 512 registers per lane, up to 160 KiB of LDS); the persistent
         projection / dX GEMM between two layers holds ceil(grid / workgroups per CU) more (occupancy from the library:
         mvae_occupancy)."""
         per, L = B // 16, len(layers)
         cus = {True: -(-self.pipe_gemm_blocks // self._occ["dx"]), False: -(-self.pipe_proj_blocks // self._occ["proj"])}
         g = max(cus.values()) if backward is None else cus[bool(backward)]
-        return L * per + (L - 1) * g + (self._n_side * per if side else 0)
+        return L * per + (L - 1) * g + n_side * per
 
-    def _pipelined(self, layers):
+    def _pipelined(self, layers, B=None):
         """ONE launch per layer for the whole sequence; layer l+1 follows layer l at a distance of ``pipe_chunk`` time
         steps, released chunk by chunk through device-side counters (include/midivae_hip.h, 'time-pipelined stacks')
         instead of one launch per (layer, chunk).  Only when every kernel of the stack can be RESIDENT together: the hardware
@@ -561,14 +556,14 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
         avoid.  The phase's other recurrences (velocity / instrument branches) wait for nobody: beside an oversubscribed chip
         they only delay the stack until they retire (decode at 1024 windows runs that way, by measurement the best schedule
         there).  Chip-filling inference batches (2048 windows: 2 x 128 + 64 workgroups) run the layers as chunk launches ordered
-        by events instead - nothing waits on the device there."""
+        by events instead - nothing waits on the device there.  ``B``: the call's padded batch (None: the engine's max_batch)."""
         if len(layers) < 2:
             return False
         T = layers[0].T
         return (self.pipeline and len(layers) - 1 <= len(self.s_layer) and T % self.pipe_chunk == 0 and
                 len(layers) * 2 * (T // self.pipe_chunk) <= 1024 and
                 all(self._il(r) for r in layers) and
-                self._resident_cus(layers, self._cur_B) <= self.num_cus)
+                self._resident_cus(layers, self.maxB if B is None else B) <= self.num_cus)
 
     def _sync_region(self, slot, n_if, nchp, nwaves, pwaves):
         """[n_if][2][nchp] 32-bit counters (hs / da chunks published, xp / dX chunks published) of pipelined stack number
@@ -586,50 +581,63 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
         # (step plans, engine_plan.py: the fields these values land in are patches - they travel as ops.CounterValue)
         return reg, ops.CounterValue(cum[0], ("sync", slot, 0)), ops.CounterValue(cum[1], ("sync", slot, 1))
 
-    def _stack_forward_pipe(self, layers, B, slot, *, states=None, h_last=None, h_last_ld=0, idx=None, start=None, xs=None,
-                            publish_top=False):
-        cs = self.pipe_chunk
-        T = layers[0].T
+    def _pipe_stack_forward(self, layers, B, slot, *, bottom=None, publish_top=False):
+        """The hand-over of a time-pipelined stack (bottom layer first) at a padded batch of B, for both schedules that launch one
+        (_stack_forward_pipe: a launch per queue; PhaseLaunches._stack_problems_forward: problems of one launch): (the pipe
+        fields of every layer, the launch of the persistent projection GEMM of every interface li -> li + 1).  ``bottom``: pipe
+        fields of a bottom layer whose input projection a producer writes out (_xpand_problem); ``publish_top``: the top layer
+        publishes its chunks too.  Advances the counters of ``slot`` (then, for a publishing top layer, of slot 10) - host-side
+        bookkeeping only, nothing is enqueued here."""
+        cs, T, L = self.pipe_chunk, layers[0].T, len(layers)
         nchp, nwaves, pwaves = T // cs, self._rnn_waves(layers[0]) * (B // 16), 4 * self.pipe_proj_blocks
-        L = len(layers)
         sync, hs_target, xp_target = self._sync_region(slot, L - 1, nchp, nwaves, pwaves)
+        self._ph.last_stack_gate = (sync[0, 0][0:1], hs_target)       # the bottom layer's first published chunk of THIS call
         status = self.store["pipe_status"]
         self._pipe_used = True
-        lower_streams = self.s_layer[:L - 1]              # layer l < L-1 on lower_streams[l]; the top layer on this stream
-        gemm_streams = self.s_proj[:L - 1]
-        self._fork(*lower_streams, *gemm_streams)
-        for li, r in enumerate(layers):
-            top = li == L - 1
-            st = states(r) if states else {}
+        pipes, gemms = [], []
+        for li in range(L):
             pipe = dict(chunk_steps=cs, status=status)
             if li > 0:
                 pipe.update(wait_ready=sync[li - 1, 1], wait_value=xp_target)
-            if not top:
+            elif bottom is not None:
+                assert bottom["chunk_steps"] == cs
+                pipe.update(bottom)
+            if li < L - 1:
                 pipe["signal_done"] = sync[li, 0]
+                gemms.append(lambda li=li: self._rec_xp(      # projection for the layer above: one persistent launch
+                    layers[li + 1], B, 0, 1, max_blocks=self.pipe_proj_blocks, chunk_rows=cs * B, chunk_wait=sync[li, 0],
+                    chunk_wait_value=hs_target, chunk_done=sync[li, 1], chunk_status=status))
             elif publish_top:
                 # (inference: the head follows the top layer slice by slice - _head_forward; a slot of its own: these counters
                 #  advance only in calls that publish)
                 sync_t, target_t, _ = self._sync_region(10, 1, nchp, nwaves, 0)
                 pipe["signal_done"] = sync_t[0, 0]
-                self._top_publish = (sync_t[0, 0], target_t, cs)
-            def run():
+                self._ph.top_publish = (sync_t[0, 0], target_t, cs)
+            pipes.append(pipe)
+        return pipes, gemms
+
+    def _stack_forward_pipe(self, layers, B, slot, *, states=None, h_last=None, h_last_ld=0, idx=None, start=None, xs=None,
+                            publish_top=False):
+        pipes, gemms = self._pipe_stack_forward(layers, B, slot, publish_top=publish_top)
+        L = len(layers)
+        lower_streams = self.s_layer[:L - 1]              # layer l < L-1 on lower_streams[l]; the top layer on this stream
+        gemm_streams = self.s_proj[:L - 1]
+        self._fork(*lower_streams, *gemm_streams)
+        for li, r in enumerate(layers):                   # (host order: layer, its projection GEMM, the layer above)
+            top = li == L - 1
+            with (contextlib.nullcontext() if top else torch.cuda.stream(lower_streams[li])):
                 self._rec_forward(r, B, 0, 1, idx=idx, start=start, xs=xs, h_last=h_last if top else None,
-                                  h_last_ld=h_last_ld if top else 0, pipe=pipe, xp_external=li > 0, **st)
-            if top:
-                run()
-            else:
-                with torch.cuda.stream(lower_streams[li]):
-                    run()
-                with torch.cuda.stream(gemm_streams[li]):     # projection for the layer above: one persistent launch
-                    self._rec_xp(layers[li + 1], B, 0, 1, max_blocks=self.pipe_proj_blocks, chunk_rows=cs * B,
-                                 chunk_wait=sync[li, 0], chunk_wait_value=hs_target, chunk_done=sync[li, 1], chunk_status=status)
+                                  h_last_ld=h_last_ld if top else 0, pipe=pipes[li], xp_external=li > 0,
+                                  **(states(r) if states else {}))
+            if not top:
+                with torch.cuda.stream(gemm_streams[li]):
+                    gemms[li]()
         self._join(*lower_streams, *gemm_streams)
 
     def _stack_forward(self, layers, B, *, states=None, h_last=None, h_last_ld=0, idx=None, start=None, slot=0, xs=None,
                        publish_top=False):
         """A stack of recurrent layers, pipelined over time chunks: layer l on stream l."""
-        self._cur_B = B
-        if self._pipelined(layers):
+        if self._pipelined(layers, B):
             return self._stack_forward_pipe(layers, B, slot, states=states, h_last=h_last, h_last_ld=h_last_ld, idx=idx,
                                             start=start, xs=xs, publish_top=publish_top)
         nch = self._nchunks(layers)
@@ -665,20 +673,18 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
         Breal, B = B, self.pad16(B)
         cat = self._v("cat", B, self.ncat * H)
         ldc = self.ncat * H
-        self._cur_B, self._n_side = B, len(self.enc_meta)
-        if not self._encoder_forward_multi(B, cat, ldc):      # (one launch for all of them: engine_phases.py)
-            self._fork_with_stack(self.enc_notes, *[st for _, st, _ in self.enc_meta])
-            for k, (r, st, src) in enumerate(self.enc_meta, 1):
-                with self._on(st):
-                    inp = (dict(xs=self._v(src, r.T, B)) if r.xmode == hl.X_SCALAR else dict(idx=self._v(src, r.T, B)))
-                    self._rec_forward(r, B, h_last=cat[:, k * H:(k + 1) * H], h_last_ld=ldc, **inp)
-            if self.enc_bi:
-                self._enc_bi_forward(B, cat[:, 0:H], ldc)
-            else:
-                self._stack_forward(self.enc_notes, B, idx=self._v("in.x_idx", s.T, B), h_last=cat[:, 0:H], h_last_ld=ldc, slot=0)
-            self._prefork = None
-            self._join(*[st for _, st, _ in self.enc_meta])
-        self._n_side = 0
+        with self._scheduling("_ph", PhaseState(n_side=len(self.enc_meta))):
+            if not self._encoder_forward_multi(B, cat, ldc):      # (one launch for all of them: engine_phases.py)
+                self._fork_with_stack(self.enc_notes, B, *[st for _, st, _ in self.enc_meta])
+                for k, (r, st, src) in enumerate(self.enc_meta, 1):
+                    with self._on(st):
+                        inp = (dict(xs=self._v(src, r.T, B)) if r.xmode == hl.X_SCALAR else dict(idx=self._v(src, r.T, B)))
+                        self._rec_forward(r, B, h_last=cat[:, k * H:(k + 1) * H], h_last_ld=ldc, **inp)
+                if self.enc_bi:
+                    self._enc_bi_forward(B, cat[:, 0:H], ldc)
+                else:
+                    self._stack_forward(self.enc_notes, B, idx=self._v("in.x_idx", s.T, B), h_last=cat[:, 0:H], h_last_ld=ldc, slot=0)
+                self._join(*[st for _, st, _ in self.enc_meta])
         self._mark("  encoder recurrences")
         self._S_done = False
         fused_hist = self._hist_fused            # (history of this minibatch from this very forward pass: train_step_begin)
@@ -736,8 +742,9 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
             self._S_done = with_init
         return ok
 
-    def decoder_forward(self, B, want_probs=False):
-        """reference vae_definition.py:519-645 (decoder heads) + losses :332-441 when targets are staged."""
+    def decoder_forward(self, B, want_probs=False, stay_forked=False):
+        """reference vae_definition.py:519-645 (decoder heads) + losses :332-441 when targets are staged.  ``stay_forked``: the
+        side heads' queues are not joined here - backward(..., stay_forked=True) follows (TrainSteps.forward_backward)."""
         s, P = self.spec, self.P
         H, T, V = s.H, s.T, s.V
         Breal, B = B, self.pad16(B)
@@ -758,28 +765,25 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
         tg = self._have_targets
         side = [h for h in self.dec_heads if h.stream is not None]
         aux_src = {a.src for a in self.aux}
-        self._cur_B, self._n_side = B, len(side)
-        multi = len(self.dec_notes) > 1 and self._phase_ok(self.dec_notes, ())      # (the notes stack is ONE launch on this queue)
-        if multi and side:
-            # the side heads leave the critical queue WITHOUT an event (a record is a packet of ~50 us between the latent chain and the
-            # decoder launch): their queues wait for the first chunk the notes stack publishes - it runs behind the latent chain
-            # (settled against an event fork, r03_z: -0.03 ms per step)
-            self._last_stack_gate = None
-            self._head_forward(self.head["notes"], B, Breal, states, tg, want_probs or "notes" in aux_src, slot=1)
-            assert self._last_stack_gate is not None, "the notes stack did not run as a phase launch"
-            word, value = self._last_stack_gate
+        multi = len(self.dec_notes) > 1 and self._phase_ok(self.dec_notes, (), B)      # (the notes stack is ONE launch on this queue)
+        with self._scheduling("_ph", PhaseState(n_side=len(side))) as ph:
+            if multi and side:
+                # the side heads leave the critical queue WITHOUT an event (a record is a packet of ~50 us between the latent chain and the
+                # decoder launch): their queues wait for the first chunk the notes stack publishes - it runs behind the latent chain
+                # (settled against an event fork, r03_z: -0.03 ms per step)
+                self._head_forward(self.head["notes"], B, Breal, states, tg, want_probs or "notes" in aux_src, slot=1)
+                assert ph.last_stack_gate is not None, "the notes stack did not run as a phase launch"
+                word, value = ph.last_stack_gate
+                for h in side:
+                    ops.stream_wait_value32(word, value, stream=h.stream)
+            elif not multi:
+                self._fork_with_stack(self.dec_notes, B, *[h.stream for h in side])
             for h in side:
-                ops.stream_wait_value32(word, value, stream=h.stream)
-        elif not multi:
-            self._fork_with_stack(self.dec_notes, *[h.stream for h in side])
-        for h in side:
-            with self._on(h.stream):
-                self._head_forward(h, B, Breal, states, tg, want_probs or h.name in aux_src or (h.kind == 1 and self._want_vel), slot=None)
-        if not (multi and side):
-            self._head_forward(self.head["notes"], B, Breal, states, tg, want_probs or "notes" in aux_src, slot=1)
-        self._prefork = None
-        self._n_side = 0
-        if not self._branches_stay_forked or self.aux:
+                with self._on(h.stream):
+                    self._head_forward(h, B, Breal, states, tg, want_probs or h.name in aux_src or (h.kind == 1 and self._want_vel), slot=None)
+            if not (multi and side):
+                self._head_forward(self.head["notes"], B, Breal, states, tg, want_probs or "notes" in aux_src, slot=1)
+        if not stay_forked or self.aux:
             self._join(*[h.stream for h in side])
         for a in self.aux:
             self._aux_forward(a, B, Breal, tg, want_probs)
@@ -789,7 +793,6 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
         s, P = self.spec, self.P
         H, n = s.H, h.name
         start = self._v("in.start_" + n, B, h.layers[0].K)
-        self._top_publish = None
         if len(h.layers) > 1 and slot is not None:
             multi = self._notes_forward_multi(h, B, states, start)      # (both layers as one launch: engine_phases.py)
             if multi and self.training:
@@ -815,9 +818,8 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
             tgt["row_weight"] = self._v("in.rw_" + n, R)
             if n == "notes" and s.attach:
                 tgt["target_idx2"] = self._v("in.ya_idx", R)
-        if self._top_publish is not None:
-            word, target, cs = self._top_publish
-            self._top_publish = None
+        if self._ph.top_publish is not None:
+            (word, target, cs), self._ph.top_publish = self._ph.top_publish, None
             nsl = self.head_slices
             Ts = h.T // nsl
             am = self._v(n + ".argmax", R)
@@ -906,102 +908,131 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
         ops.gemm(da.view(Tc * B, GH), self._v(p + ".wc", H, GH), dx, Tc * B, H, GH, trans_b=True, c_layout=self.lay,
                  **chunked)
 
-    def _stack_backward_pipe(self, layers, B, slot, *, dhs_ext=None, dh_last=None, dh_last_ld=0, dstates=None, idx=None,
-                             xs=None, start=None):
-        cs = self.pipe_chunk
-        T = layers[0].T
+    def _pipe_stack_backward(self, layers, B, slot):
+        """The hand-over of a time-pipelined stack's BPTT (TOP layer first: it runs first and publishes da) at a padded batch of
+        B, for both schedules (_stack_backward_pipe, PhaseLaunches._stack_problems_backward): (the pipe fields of every layer,
+        the launch of the persistent dX GEMM below every layer but the bottom one, (sync, da_target, chunks) for whatever is
+        released by a layer's published da: row li of ``sync`` is order[li]'s, row L-1 the bottom layer's).  Advances the
+        counters of ``slot``; nothing is enqueued here."""
+        cs, T = self.pipe_chunk, layers[0].T
         nchp, nwaves, pwaves = T // cs, self._rnn_waves(layers[0]) * (B // 16), 4 * self.pipe_gemm_blocks
-        order = list(reversed(layers))               # order[0] = top layer: runs on this stream, publishes da
+        order = list(reversed(layers))
         L = len(order)
-        kstream = self._kstream_ok(layers, B)
-        if kstream:
-            before = self._ev_record(torch.cuda.current_stream())      # the layers' saved inputs and the zeroed gradient buffers
-        sync, da_target, dx_target = self._sync_region(slot, L, nchp, nwaves, pwaves)     # (row L-1: the bottom layer's da)
+        sync, da_target, dx_target = self._sync_region(slot, L, nchp, nwaves, pwaves)
         status = self.store["pipe_status"]
         self._pipe_used = True
-        lower_streams = self.s_layer[:L - 1]         # order[li], li >= 1, on lower_streams[li - 1]
-        gemm_streams = self.s_proj[:L - 1]
-        self._fork(*lower_streams, *gemm_streams)
+        pipes, gemms = [], []
         for li, r in enumerate(order):
-            top = li == 0
-            ds = dstates(r) if dstates else {}
             # EVERY layer publishes its da chunks, the bottom one too, whether or not a K-streaming launch follows it in THIS
             # call: the counters are cumulative over calls (_sync_region), so a row that is only advanced by some calls - the
             # K-streaming decision depends on the call's batch - would fall behind its thresholds for good (0.03 us per step)
             pipe = dict(chunk_steps=cs, status=status, signal_done=sync[li, 0])
             if li > 0:
                 pipe.update(wait_ready=sync[li - 1, 1], wait_value=dx_target)
-            def run():
+            pipes.append(pipe)
+            if li < L - 1:
+                gemms.append(lambda li=li, r=r: self._rec_dx(       # dX for the layer below, from the last chunk to the first
+                    r, B, 0, 1, max_blocks=self.pipe_gemm_blocks, chunk_rows=cs * B, chunk_reverse=True, chunk_wait=sync[li, 0],
+                    chunk_wait_value=da_target, chunk_done=sync[li, 1], chunk_status=status))
+        return pipes, gemms, (sync, da_target, nchp)
+
+    def _ks(self, counters, target, cs, B):
+        """what a K-streaming problem follows (ParamGradients._kstream_problems): a layer's published da chunks of cs steps"""
+        return dict(counters=counters, target=target, rows=cs * B, status=self.store["pipe_status"])
+
+    def _launch_kstream(self, problems, gates, bottom_word, target):
+        """the K-streaming weight-gradient launch of a stack on the second gradient queue, behind ``gates`` ((word, value): the
+        last chunk of every single-layer branch whose dU GEMM joined it) and the stack's bottom layer.
+        Its workgroups wait, resident, for the whole BPTT: they may only take CUs once EVERY kernel they wait for is running
+        (a recurrent workgroup needs a whole empty CU) - the queue holds the launch back until the BOTTOM layer has
+        published its first chunk, which it can only do with the layers above it and the dX GEMMs running too."""
+        for word, value in gates:
+            ops.stream_wait_value32(word, value, stream=self.s_grad2)
+        ops.stream_wait_value32(bottom_word, target, stream=self.s_grad2)
+        with torch.cuda.stream(self.s_grad2):
+            ops.gemm_kstream_multi(problems)
+
+    def _stack_backward_pipe(self, layers, B, slot, *, dhs_ext=None, dh_last=None, dh_last_ld=0, dstates=None, idx=None,
+                             xs=None, start=None):
+        cs = self.pipe_chunk
+        order = list(reversed(layers))               # order[0] = top layer: runs on this stream, publishes da
+        L = len(order)
+        kstream = self._kstream_ok(layers, B, self._ph.n_side, deferring=self._call.deferred_gemms is not None)
+        if kstream:
+            before = self._ev_record(torch.cuda.current_stream())      # the layers' saved inputs and the zeroed gradient buffers
+        pipes, gemms, (sync, da_target, nchp) = self._pipe_stack_backward(layers, B, slot)
+        lower_streams = self.s_layer[:L - 1]         # order[li], li >= 1, on lower_streams[li - 1]
+        gemm_streams = self.s_proj[:L - 1]
+        self._fork(*lower_streams, *gemm_streams)
+        for li, r in enumerate(order):               # (host order: layer, its gradient work, the dX GEMM below it, the next layer)
+            top = li == 0
+            with (contextlib.nullcontext() if top else torch.cuda.stream(lower_streams[li - 1])):
                 ext = dhs_ext if top else self._v(order[li - 1].prefix + ".dx", r.T, B, self.spec.H)
                 self._rec_bptt(r, B, 0, 1, dhs_ext=ext, dh_last=dh_last if top else None,
-                               dh_last_ld=dh_last_ld if top else 0, pipe=pipe, **ds)
+                               dh_last_ld=dh_last_ld if top else 0, pipe=pipes[li], **(dstates(r) if dstates else {}))
                 if not kstream:
                     self._rec_param_grads(r, B, idx=idx, xs=xs, start=start, publishes=(sync[li, 0], da_target, cs))
-            if top:
-                run()
-            else:
-                with torch.cuda.stream(lower_streams[li - 1]):
-                    run()
             if li < L - 1:
-                with torch.cuda.stream(gemm_streams[li]):     # dX for the layer below, from the last chunk to the first
-                    self._rec_dx(r, B, 0, 1, max_blocks=self.pipe_gemm_blocks, chunk_rows=cs * B, chunk_reverse=True,
-                                 chunk_wait=sync[li, 0], chunk_wait_value=da_target, chunk_done=sync[li, 1], chunk_status=status)
+                with torch.cuda.stream(gemm_streams[li]):
+                    gemms[li]()
         # chained join: the latest finisher (the bottom layer) last - ahead of the dX GEMMs it would put two hops in series
         if kstream:     # behind every kernel of the stack in host order: the recurrences are dispatched first
             problems = []
             for li, r in enumerate(order):
-                problems += self._kstream_problems(r, B, idx, dict(counters=sync[li, 0], target=da_target, rows=cs * B, status=status))
+                problems += self._kstream_problems(r, B, idx, self._ks(sync[li, 0], da_target, cs, B))
             gates = []
-            for extra, word, value in (self._kstream_extra or ()):       # single-layer branches launched before this stack (backward)
+            for extra, word, value in (self._ph.kstream_extra or ()):       # single-layer branches launched before this stack (backward)
                 if len(problems) + len(extra) <= 8:
                     problems += extra
                     gates.append((word, value))
-            self._kstream_extra = None
+            self._ph.kstream_extra = None
             self._ev_wait(self.s_grad2, before)
-            for word, value in gates:
-                ops.stream_wait_value32(word, value, stream=self.s_grad2)
-            # Its workgroups wait, resident, for the whole BPTT: they may only take CUs once EVERY kernel they wait for is running
-            # (a recurrent workgroup needs a whole empty CU) - the queue holds the launch back until the BOTTOM layer has
-            # published its first chunk, which it can only do with the layers above it and the dX GEMMs running too.
-            ops.stream_wait_value32(sync[L - 1, 0][nchp - 1:nchp], da_target, stream=self.s_grad2)
-            with torch.cuda.stream(self.s_grad2):
-                ops.gemm_kstream_multi(problems)
+            self._launch_kstream(problems, gates, sync[L - 1, 0][nchp - 1:nchp], da_target)
         self._join(*gemm_streams, *lower_streams)
+
+    def _single_bptt_publishing(self, r, B, slot, cs, *, build=False, **kw):
+        """a single-layer BPTT as ONE launch (``build``: one problem of a phase launch) that publishes its da every ``cs`` steps on
+        the counters of sync slot ``slot`` - nobody waits for them inside a stack; they release the layer's gradient work.
+        Returns (counters, target, the problem or None)."""
+        sync, target, _ = self._sync_region(slot, 1, r.T // cs, self._rnn_waves(r) * (B // 16), 0)
+        self._pipe_used = True
+        prob = self._rec_bptt(r, B, 0, 1, build=build, **kw,
+                              pipe=dict(chunk_steps=cs, status=self.store["pipe_status"], signal_done=sync[0, 0]))
+        return sync[0, 0], target, prob
+
+    def _follower_room(self):
+        """has the encoder stack's K-streaming launch (at most 8 problems) room for the dU GEMM(s) of one single-layer branch?"""
+        s = self.spec
+        return (2 if s.cell == "GRU" else 1) + (3 if s.cell == "GRU" else 2) * len(self.enc_notes) <= 8
 
     def _stack_backward(self, layers, B, *, dhs_ext=None, dh_last=None, dh_last_ld=0, dstates=None, idx=None, xs=None,
                         start=None, slot=0, kstream_extra=None):
         """BPTT through a stack (top layer first), pipelined over time chunks in reverse order."""
-        self._cur_B = B
-        if self._pipelined(layers):
+        ph = self._ph
+        if self._pipelined(layers, B):
             return self._stack_backward_pipe(layers, B, slot, dhs_ext=dhs_ext, dh_last=dh_last, dh_last_ld=dh_last_ld,
                                              dstates=dstates, idx=idx, xs=xs, start=start)
         nch = self._nchunks(layers)
         order = list(reversed(layers))               # order[0] = top layer
-        if kstream_extra is not None and len(layers) == 1 and nch == 1:
-            # a single-layer branch beside a K-streaming stack: ONE launch that publishes its da chunk by chunk (nobody waits inside
-            # the stack), its dU GEMM joins the stack's K-streaming launch, the rest of its gradients follows its end as usual
+        if len(layers) == 1 and nch == 1:
             r, cs = layers[0], self.pipe_chunk
-            sync, target, _ = self._sync_region(4, 1, r.T // cs, self._rnn_waves(r) * (B // 16), 0)
-            self._rec_bptt(r, B, 0, 1, dhs_ext=dhs_ext, dh_last=dh_last, dh_last_ld=dh_last_ld,
-                           pipe=dict(chunk_steps=cs, status=self.store["pipe_status"], signal_done=sync[0, 0]),
-                           **(dstates(r) if dstates else {}))
-            ks = dict(counters=sync[0, 0], target=target, rows=cs * B, status=self.store["pipe_status"])
-            kstream_extra.append((self._kstream_problems(r, B, idx, ks, only_dU=True), sync[0, 0][r.T // cs - 1:r.T // cs], target))
-            self._rec_param_grads(r, B, idx=idx, xs=xs, start=start, skip_dU=True)
-            return
-        if (len(layers) == 1 and nch == 1 and self._grad_portion_jobs is not None and self.pipeline and
-                self._il(layers[0]) and layers[0].T % self.pipe_chunk == 0 and
-                self._portion_count(layers[0], B, self.pipe_chunk) > 1 and self._single_slot < self._single_slot_end):
-            # a full-length single-layer branch whose gradients go in time portions: ONE launch that publishes its da chunks
-            r, cs = layers[0], self.pipe_chunk
-            sync, target, _ = self._sync_region(11 + self._single_slot, 1, r.T // cs, self._rnn_waves(r) * (B // 16), 0)
-            self._single_slot += 1
-            self._pipe_used = True
-            self._rec_bptt(r, B, 0, 1, dhs_ext=dhs_ext, dh_last=dh_last, dh_last_ld=dh_last_ld,
-                           pipe=dict(chunk_steps=cs, status=self.store["pipe_status"], signal_done=sync[0, 0]),
-                           **(dstates(r) if dstates else {}))
-            self._rec_param_grads(r, B, idx=idx, xs=xs, start=start, publishes=(sync[0, 0], target, cs))
-            return
+            bptt = dict(dhs_ext=dhs_ext, dh_last=dh_last, dh_last_ld=dh_last_ld, **(dstates(r) if dstates else {}))
+            if kstream_extra is not None:
+                # a single-layer branch beside a K-streaming stack: ONE launch that publishes its da chunk by chunk (nobody waits
+                # inside the stack), its dU GEMM joins the stack's K-streaming launch, the rest of its gradients follows its end
+                # as usual
+                counters, target, _ = self._single_bptt_publishing(r, B, 4, cs, **bptt)
+                kstream_extra.append((self._kstream_problems(r, B, idx, self._ks(counters, target, cs, B), only_dU=True),
+                                      counters[r.T // cs - 1:r.T // cs], target))
+                self._rec_param_grads(r, B, idx=idx, xs=xs, start=start, skip_dU=True)
+                return
+            if (ph.grad_portion_jobs is not None and self.pipeline and self._il(r) and r.T % cs == 0 and
+                    self._portion_count(r, B, cs) > 1 and ph.single_slot < ph.single_slot_end):
+                # a full-length single-layer branch whose gradients go in time portions: ONE launch that publishes its da chunks
+                slot1, ph.single_slot = 11 + ph.single_slot, ph.single_slot + 1
+                counters, target, _ = self._single_bptt_publishing(r, B, slot1, cs, **bptt)
+                self._rec_param_grads(r, B, idx=idx, xs=xs, start=start, publishes=(counters, target, cs))
+                return
         streams = [None] + self.s_layer[:len(layers) - 1]
         done = [[None] * nch for _ in order]
         if nch > 1:
@@ -1021,10 +1052,10 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
                     if nch > 1:
                         done[li][k] = self._ev_record(torch.cuda.current_stream())
                     if k == 0:
-                        if self._hold_side and self._after_chain is not None and idx is None and xs is None:
+                        if ph.hold_side and self._call.after_chain is not None and idx is None and xs is None:
                             # (a decoder side head beside a K-streaming notes stack: its gradient GEMMs would start at the end of
                             #  the phase and run across the latent chain - they wait for the encoder launch's first chunk instead)
-                            self._after_chain.append(lambda r=r: dict(r=r, B=B, start=start))
+                            self._call.after_chain.append(lambda r=r: dict(r=r, B=B, start=start))
                         else:
                             self._rec_param_grads(r, B, idx=idx, xs=xs, start=start)
                 if li > 0 and nch > 1:
@@ -1046,7 +1077,7 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
     def _head_stack_backward(self, h, B, dstates, slot):
         """output Dense backward + BPTT through one decoder head's cell stack"""
         start = self._v("in.start_" + h.name, B, h.layers[0].K)
-        if len(h.layers) > 1 and slot is not None and self._phase_ok(h.layers, ()):
+        if len(h.layers) > 1 and slot is not None and self._phase_ok(h.layers, (), B):
             dext, head_grads = self._head_backward(B, h.name, h.layers[-1], h.N, h.NP, h.out + ".W", h.out + ".b", defer=True)
             self._notes_backward_multi(h, B, dext, dstates, start, head_grads)
             return
@@ -1076,7 +1107,7 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
             self._small(lambda: ops.colsum(dl, R, N, G[outb], ldx=NP))
         if defer:
             return dhs, grads
-        if self._deferred_gemms is not None:        # (collected, not enqueued: no fork)
+        if self._call.deferred_gemms is not None:        # (collected, not enqueued: no fork)
             grads()
             return dhs
         self._fork(self.s_grad)
@@ -1084,8 +1115,13 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
             grads()
         return dhs
 
-    def backward(self, B):
-        """Reverse of encoder_forward/decoder_forward; accumulates into self.grads (zeroed by the caller)."""
+    def backward(self, B, stay_forked=False):
+        """Reverse of encoder_forward/decoder_forward; accumulates into self.grads (zeroed by the caller).  ``stay_forked``: the
+        side heads' queues were left forked by decoder_forward(..., stay_forked=True)."""
+        with self._scheduling("_call", CallState()) as call:
+            self._backward(B, stay_forked, call)
+
+    def _backward(self, B, stay_forked, call):
         s, P, G = self.spec, self.P, self.G
         H, Z, T, V = s.H, s.Z, s.T, s.V
         Breal, B = B, self.pad16(B)
@@ -1100,51 +1136,53 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
         # ---- decoder: the notes stack and the side heads, independent branches -----------------------------------
         # (one event for the branches, the notes head's gradient GEMM and the notes stack's lower layers)
         side = [h for h in self.dec_heads if h.stream is not None]
-        self._cur_B, self._n_side = B, len(side)
-        self._deferred_gemms = [] if self._defers_grads(B) else None
-        for a in self.aux:
-            self._aux_backward(a, B)
-        notes_multi = len(self.dec_notes) > 1 and self._phase_ok(self.dec_notes, ())     # (one launch, gradient work by counters)
-        if not notes_multi and self.grad_portions:       # (per-queue schedule: long sequences release their gradient work in portions)
-            self._grad_portion_jobs, self._single_slot, self._single_slot_end = [], 0, 3      # (decoder: sync slots 11..13)
+        call.deferred_gemms = [] if self._defers_grads(B) else None
+        deferring = call.deferred_gemms is not None
+        notes_multi = len(self.dec_notes) > 1 and self._phase_ok(self.dec_notes, (), B)     # (one launch, gradient work by counters)
         # (data parallel with the early bucket - _bucket_hook - : every decoder-side gradient has to be QUEUED when the bucket's
         #  collective is issued, in front of the encoder launch: nothing is held back behind it then -
         #  test_nothing_is_added_to_the_decoder_bucket_after_its_collective_was_issued)
         early_bucket = self._bucket_hook is not None and self.layout.dec_begin > 0
-        self._after_chain = [] if (notes_multi and not self.enc_bi and len(self.enc_notes) > 1 and not early_bucket and
-                                   self._phase_ok(self.enc_notes, [r for r, _, _ in self.enc_meta])) else None
-        if self._branches_stay_forked:      # (train step: the side heads' queues go straight on with their own backward)
-            if not notes_multi:
-                self._fork_with_stack(self.dec_notes, also=(self.s_grad,))
-        elif notes_multi:
-            if side:
-                self._fork(*[h.stream for h in side])
-        else:
-            self._fork_with_stack(self.dec_notes, *[h.stream for h in side], also=(self.s_grad,))
-        if notes_multi and self._decoder_kstream_ok(self.dec_notes, B):
-            self._grad_streams = (self.s_grad, self.s_grad)      # the second gradient queue holds the notes stack's K-streaming launch
-            self._hold_side = True
-        for h in side:
-            with self._on(h.stream):
-                self._head_stack_backward(h, B, dstates, slot=None)
-        self._hold_side = False
-        self._head_stack_backward(self.head["notes"], B, dstates, slot=2)
-        if notes_multi:
-            self._pace_point(4)              # (the encoder phase may be enqueued while the latent chain runs)
-        self._grad_streams = None
-        self._prefork = None
-        self._flush_grad_portions()
+        with self._scheduling("_ph", PhaseState(n_side=len(side))) as ph:
+            for a in self.aux:
+                self._aux_backward(a, B)
+            if not notes_multi and self.grad_portions:       # (per-queue schedule: long sequences release their gradient work in portions)
+                ph.grad_portion_jobs, ph.single_slot, ph.single_slot_end = [], 0, 3      # (decoder: sync slots 11..13)
+            call.after_chain = [] if (notes_multi and not self.enc_bi and len(self.enc_notes) > 1 and not early_bucket and
+                                      self._phase_ok(self.enc_notes, [r for r, _, _ in self.enc_meta], B)) else None
+            if stay_forked:      # (train step: the side heads' queues go straight on with their own backward)
+                if not notes_multi:
+                    self._fork_with_stack(self.dec_notes, B, also=(self.s_grad,))
+            elif notes_multi:
+                if side:
+                    self._fork(*[h.stream for h in side])
+            else:
+                self._fork_with_stack(self.dec_notes, B, *[h.stream for h in side], also=(self.s_grad,))
+            # The decoder notes stack's weight gradients are a K-streaming launch too (_decoder_kstream_ok), the side heads' gradient
+            # GEMMs are held behind the latent chain beside it (hold_side), and the dU GEMM of a full-length single-layer encoder
+            # branch joins the encoder's K-streaming launch (kstream_extra, below) (settled r02: LSTM 7.60 -> 7.50 ms, GRU
+            # 6.55 -> 6.38; profiles/r02_n_ab_kstream_gradients.txt)
+            if notes_multi and self._decoder_kstream_ok(self.dec_notes, B, ph.n_side, deferring=deferring):
+                ph.grad_streams = (self.s_grad, self.s_grad)      # the second gradient queue holds the notes stack's K-streaming launch
+                ph.hold_side = True      # (read by the side heads only: the notes stack of such a step is a phase launch)
+            for h in side:
+                with self._on(h.stream):
+                    self._head_stack_backward(h, B, dstates, slot=None)
+            self._head_stack_backward(self.head["notes"], B, dstates, slot=2)
+            if notes_multi:
+                self._pace_point(4)              # (the encoder phase may be enqueued while the latent chain runs)
+        self._flush_grad_portions(ph.grad_portion_jobs)      # (behind the phase: on the gradient queues proper, nothing preforked)
         self._join(*[h.stream for h in side], word=0)
         self._mark("  decoder BPTT")
         # (the signature head adds to d(z) between the initial-state Denses and the latent block: separate launches then)
-        enc_multi = not self.enc_bi and self._phase_ok(self.enc_notes, [r for r, _, _ in self.enc_meta]) and len(self.enc_notes) > 1
-        self._deferred_side = [] if (enc_multi and not early_bucket) else None       # (released by the encoder launch's first published chunk)
+        enc_multi = not self.enc_bi and self._phase_ok(self.enc_notes, [r for r, _, _ in self.enc_meta], B) and len(self.enc_notes) > 1
+        call.deferred_side = [] if (enc_multi and not early_bucket) else None       # (released by the encoder launch's first published chunk)
         dcat = (self._latent_chain_backward(Breal, B)
                 if (self.fused_latent and self._chain_ok() and not s.signature) else None)
         if dcat is None:
             self._chain_refused_now()
             dcat = self._latent_backward_unfused(Breal, B)
-        latent_grads, self._deferred_side = self._deferred_side, None
+        latent_grads, call.deferred_side = call.deferred_side, None
         self._pace(4)
         ldc = self.ncat * H
         self._mark("  latent block backward")
@@ -1159,46 +1197,41 @@ class Engine(Buffers, ArrayStaging, OptionalGraph, PhaseLaunches, PlannedSteps, 
             with torch.cuda.stream(self.s_comm):
                 self._host_call("early", lambda: hook.early(self.grads[self.layout.dec_begin:self.layout.total]))
         # ---- encoder recurrences: the notes stack and the meta rolls, independent branches ---------------------------
-        self._cur_B, self._n_side = B, len(self.enc_meta)
-        enc_one_launch = bool(enc_multi and self._encoder_backward_multi(B, dcat, ldc, latent_grads))      # (one launch: engine_phases.py)
-        if not enc_one_launch:
-            assert not latent_grads
-            if self.grad_portions:
-                self._grad_portion_jobs, self._single_slot, self._single_slot_end = [], 3, 5      # (encoder: 14..15 - disjoint: the counters are cumulative per slot)
-            ks_extra = None
-            if not self.enc_bi and self._kstream_ok(self.enc_notes, B):
-                self._grad_streams = (self.s_grad, self.s_grad)     # the second gradient queue holds the notes stack's K-streaming launch
-                ks_extra = self._kstream_extra = []
-            self._fork_with_stack(self.enc_notes, *[st for _, st, _ in self.enc_meta])
-            for k, (r, st, src) in enumerate(self.enc_meta, 1):
-                with self._on(st):
-                    inp = (dict(xs=self._v(src, r.T, B)) if r.xmode == hl.X_SCALAR else dict(idx=self._v(src, r.T, B)))
-                    follow = (ks_extra is not None and not ks_extra and r.T == T and
-                              self._il(r) and r.xmode != hl.X_CONST and
-                              (2 if s.cell == "GRU" else 1) + (3 if s.cell == "GRU" else 2) * len(self.enc_notes) <= 8)
-                    self._stack_backward([r], B, dh_last=dcat[:, k * H:(k + 1) * H], dh_last_ld=ldc,
-                                         kstream_extra=ks_extra if follow else None, **inp)
-            if self.enc_bi:
-                self._enc_bi_backward(B, dcat[:, 0:H], ldc)
-            else:
-                self._stack_backward(self.enc_notes, B, dh_last=dcat[:, 0:H], dh_last_ld=ldc, idx=self._v("in.x_idx", T, B), slot=3)
-            self._prefork = None
-            self._grad_streams = None
-            self._flush_grad_portions()
-        self._n_side = 0
+        with self._scheduling("_ph", PhaseState(n_side=len(self.enc_meta))) as ph:
+            enc_one_launch = bool(enc_multi and self._encoder_backward_multi(B, dcat, ldc, latent_grads))      # (one launch: engine_phases.py)
+            if not enc_one_launch:
+                assert not latent_grads
+                if self.grad_portions:
+                    ph.grad_portion_jobs, ph.single_slot, ph.single_slot_end = [], 3, 5      # (encoder: 14..15 - disjoint: the counters are cumulative per slot)
+                if not self.enc_bi and self._kstream_ok(self.enc_notes, B, ph.n_side, deferring=deferring):
+                    ph.grad_streams = (self.s_grad, self.s_grad)     # the second gradient queue holds the notes stack's K-streaming launch
+                    ph.kstream_extra = []
+                ks_extra = ph.kstream_extra
+                self._fork_with_stack(self.enc_notes, B, *[st for _, st, _ in self.enc_meta])
+                for k, (r, st, src) in enumerate(self.enc_meta, 1):
+                    with self._on(st):
+                        inp = (dict(xs=self._v(src, r.T, B)) if r.xmode == hl.X_SCALAR else dict(idx=self._v(src, r.T, B)))
+                        follow = (ks_extra is not None and not ks_extra and r.T == T and
+                                  self._il(r) and r.xmode != hl.X_CONST and self._follower_room())
+                        self._stack_backward([r], B, dh_last=dcat[:, k * H:(k + 1) * H], dh_last_ld=ldc,
+                                             kstream_extra=ks_extra if follow else None, **inp)
+                if self.enc_bi:
+                    self._enc_bi_backward(B, dcat[:, 0:H], ldc)
+                else:
+                    self._stack_backward(self.enc_notes, B, dh_last=dcat[:, 0:H], dh_last_ld=ldc, idx=self._v("in.x_idx", T, B), slot=3)
+        self._flush_grad_portions(ph.grad_portion_jobs)
         # the two gradient queues finish last and together: chained, they would put two cross-queue hops in series - the
         # early finishers are chained into one of them, the other is waited for directly
         # Phase launches: the persistent projection / dX GEMMs on their own queue are NOT waited for here - the launch that consumed
         # their last chunk has ended on this queue, so they have written everything (they exit behind their last publish), and their
         # queue orders them against the next step's GEMMs; the encoder rolls' queues carried nothing in this phase.  Every stream
         # in this join is one more cross-queue hop (40-60 us each, in series) in front of the optimizer.
-        tail = self._tail_streams if enc_multi else [st for _, st, _ in self.enc_meta]
-        self._tail_streams = []
+        tail = call.tail_streams if enc_multi else [st for _, st, _ in self.enc_meta]
         # Round 6: a step that collects its weight-gradient GEMMs (defer_grads_rows) and ran every encoder recurrence as ONE launch on
         # this queue has everything its collected GEMMs read right here - they go out BEFORE the joins, beside what the gradient
         # queues still have to do (the decoder side's early launch and its small reductions), instead of behind two cross-queue hops
         # (reference shape: the critical queue sat 0.16 ms in those waits with 0.09 ms of its own work still to come).
-        flush_first = self.flush_before_join and enc_one_launch and self._deferred_gemms is not None
+        flush_first = self.flush_before_join and enc_one_launch and call.deferred_gemms is not None
         if flush_first:
             self._flush_deferred_gemms()
         self._join(*tail, self.s_grad, word=1)

@@ -42,7 +42,7 @@ class ParamGradients(object):
         round 2 tried it at T=512 x 256 windows, where a portion was all atomic epilogue), and only the last one is left when the
         recurrence ends.  Portions of all layers of a phase are enqueued portion-major (_flush_grad_portions): a queue parked on
         one layer's last chunk must not hold another layer's first portions."""
-        if publishes is None or self._grad_portion_jobs is None:
+        if publishes is None or self._ph.grad_portion_jobs is None:
             return 1
         return self._portion_count(r, B, publishes[2])
 
@@ -55,9 +55,9 @@ class ParamGradients(object):
             P -= 1
         return max(P, 1)
 
-    def _flush_grad_portions(self):
-        """launch the collected gradient portions of a phase, portion-major (first portions of every layer first)"""
-        jobs, self._grad_portion_jobs = self._grad_portion_jobs, None
+    def _flush_grad_portions(self, jobs):
+        """launch the gradient portions a phase collected (PhaseState.grad_portion_jobs), portion-major (first portions of every
+        layer first)"""
         for _, fn in sorted(jobs or [], key=lambda j: j[0]):
             fn()
 
@@ -66,8 +66,8 @@ class ParamGradients(object):
         or, on a step that defers them (defer_grads_rows), kept as a problem of the one mvae_gemm_multi launch behind the last
         recurrence"""
         # (the fast kernel's shapes: whole 128-column tiles, one narrow tile, or - a wide head's dW - whole tiles and a narrow last one)
-        if self._deferred_gemms is not None and self.tile16 and K % 64 == 0 and (N % 128 == 0 or N < 128 or kw.get("colsum_b") is None):
-            self._deferred_gemms.append(ops.gemm(A, Bm, C, M, N, K, trans_a=True, accumulate=True, build_only=True, **kw))
+        if self._call.deferred_gemms is not None and self.tile16 and K % 64 == 0 and (N % 128 == 0 or N < 128 or kw.get("colsum_b") is None):
+            self._call.deferred_gemms.append(ops.gemm(A, Bm, C, M, N, K, trans_a=True, accumulate=True, build_only=True, **kw))
             return
         ops.gemm(A, Bm, C, M, N, K, trans_a=True, accumulate=True, **kw)
 
@@ -75,8 +75,8 @@ class ParamGradients(object):
         """a small launch of the parameter-gradient work (a column sum, a sum over time): now on the current stream - or, on a
         step that defers (defer_grads_rows), behind the batched GEMM launch on the critical queue (a gate + a launch on a gradient
         queue costs the command processors more than these kernels run)"""
-        if self._deferred_gemms is not None:
-            self._deferred_small.append(fn)
+        if self._call.deferred_gemms is not None:
+            self._call.deferred_small.append(fn)
         else:
             fn()
 
@@ -86,8 +86,9 @@ class ParamGradients(object):
         ``early`` = (counter word, value): what has been collected SO FAR (the decoder side, the latent block) leaves now, on the
         gradient queue, released on the device by the running encoder launch's first published chunk - its workgroups are
         resident then, the GEMMs take the CUs it left empty - and the collection goes on for the encoder's own gradients."""
-        probs, small = self._deferred_gemms, self._deferred_small
-        self._deferred_gemms, self._deferred_small = ([] if early is not None else None), []
+        call = self._call
+        probs, small = call.deferred_gemms, call.deferred_small
+        call.deferred_gemms, call.deferred_small = ([] if early is not None else None), []
         if early is not None:
             if not probs and not small:
                 return
@@ -122,7 +123,7 @@ class ParamGradients(object):
             for pi in range(P):                      # BPTT order: the LAST steps first
                 t_lo = r.T - (pi + 1) * Tp
                 g = (counters[t_lo // cs:t_lo // cs + 1], target)
-                self._grad_portion_jobs.append((pi, lambda t_lo=t_lo, g=g, pi=pi: self._rec_param_grads_rows(
+                self._ph.grad_portion_jobs.append((pi, lambda t_lo=t_lo, g=g, pi=pi: self._rec_param_grads_rows(
                     r, B, idx=idx, xs=xs, start=start, skip_dU=skip_dU, gate=g, rows=(t_lo, t_lo + Tp), first=pi == 0)))
             return
         return self._rec_param_grads_rows(r, B, idx=idx, xs=xs, start=start, skip_dU=skip_dU, gate=gate, rows=rows)
@@ -147,8 +148,8 @@ class ParamGradients(object):
         if xs is not None:
             xs = xs[t_lo:t_hi]
         sk = self._split_k(R)
-        sg1, sg2 = self._grad_streams or (self.s_grad, self.s_grad2)
-        deferring = self._deferred_gemms is not None
+        sg1, sg2 = self._ph.grad_streams or (self.s_grad, self.s_grad2)
+        deferring = self._call.deferred_gemms is not None
         if deferring:                       # (everything below is collected: nothing is enqueued on the gradient queues now)
             on1 = on2 = contextlib.nullcontext()
         else:
@@ -206,21 +207,23 @@ class ParamGradients(object):
                     lower = self._v(r.lower.prefix + ".hs", T + 1, B, H)[1 + t_lo:1 + t_hi].reshape(R, H)
                     self._wgemm(lower, da2, G[p + ".W"], H, GH, R, split_k=sk)
 
-    def _kstream_ok(self, layers, B):
-        """K-streaming weight-gradient GEMMs behind the BPTT kernels of this stack?  Every layer's gradients must be GEMMs (index
-        or dense input, bias gradient fused), at most 8 of them - and their workgroups, which wait RESIDENT for the whole BPTT,
+    def _kstream_ok(self, layers, B, n_side, deferring=False):
+        """K-streaming weight-gradient GEMMs behind the BPTT kernels of this stack, in a call of B (padded) windows with ``n_side``
+        single-layer recurrences beside it (``deferring``: the call collects its gradient GEMMs, _defers_grads: never then)?
+        Every layer's gradients must be GEMMs (index or dense input, bias gradient fused), at most 8 of them - and their
+        workgroups, which wait RESIDENT for the whole BPTT,
         must find their CUs beside the stack's own kernels and the phase's other recurrences: a workgroup that only gets its CU
         when another one retires does its whole share after the recurrence, which is the tail the launch exists to remove.
         (At 256 windows: 256 - (32 + 32 + 32) = 160 free CUs for 128 workgroups - the single-layer branch's 32 on top are the ones
         that may start late; at 512 windows 96: ordinary GEMMs then, as measured, profiles/r02_q_pipe_chunk_by_batch.txt.)"""
         s = self.spec
         count = (3 if s.cell == "GRU" else 2) * len(layers)      # GEMMs per layer: dU (GRU: two launches) and dW
-        if not (self.kstream_grads and self._deferred_gemms is None and self.tile16 and count <= 8 and
-                self._pipelined(layers) and all(r.xmode in (hl.X_INDEX, hl.X_DENSE) for r in layers)):
+        if not (self.kstream_grads and not deferring and self.tile16 and count <= 8 and
+                self._pipelined(layers, B) and all(r.xmode in (hl.X_INDEX, hl.X_DENSE) for r in layers)):
             return False
         if B > self.kstream_max_B:       # (a chunk's rows grow with the batch, the time the BPTT takes for it does not)
             return False
-        free = (self.num_cus - self._resident_cus(layers, B, backward=True, side=True)) * self._occ["kstream"]
+        free = (self.num_cus - self._resident_cus(layers, B, backward=True, n_side=n_side)) * self._occ["kstream"]
         return free >= self.kstream_wgs * count + self._wide_table_wgs(layers, B)
 
     def _wide_table_wgs(self, layers, B):
@@ -235,12 +238,12 @@ class ParamGradients(object):
                 extra += max(0, wgs - self.kstream_wgs)
         return extra
 
-    def _decoder_kstream_ok(self, layers, B):
+    def _decoder_kstream_ok(self, layers, B, n_side, deferring=False):
         """the decoder notes stack's weight gradients as a K-streaming launch behind its BPTT launch?  As _kstream_ok, for a stack
         whose bottom cell steps on a constant ALL-ZERO start row (what the reference's packers pass, vae_definition.py:820,916: its
         input-kernel gradient is zero and its bias gradient the column sums of da, fused into the dU GEMM)."""
         s = self.spec
-        if not (self.kstream_grads and self._deferred_gemms is None and self.tile16 and self._pipelined(layers) and
+        if not (self.kstream_grads and not deferring and self.tile16 and self._pipelined(layers, B) and
                 B <= self.kstream_max_B and not self._diag_no_param_grads):
             return False
         bottom, rest = layers[0], layers[1:]
@@ -250,7 +253,7 @@ class ParamGradients(object):
         count = per * len(layers) + len(rest)
         if count > 8:
             return False
-        free = (self.num_cus - self._resident_cus(layers, B, backward=True, side=True)) * self._occ["kstream"]
+        free = (self.num_cus - self._resident_cus(layers, B, backward=True, n_side=n_side)) * self._occ["kstream"]
         return free >= self.kstream_wgs * count
 
     def _kstream_problems(self, r, B, idx, ks, only_dU=False):

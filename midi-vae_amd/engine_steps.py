@@ -67,15 +67,12 @@ class TrainSteps(object):
         # The velocity / instrument branches' backward depends on nothing the notes branch does in between: no join at
         # the end of the decoder forward pass and no fork at the start of the backward pass (two packets less on the
         # critical queue); they are joined where the decoder BPTT ends.
-        self._branches_stay_forked = not self.aux
-        try:
-            self._pace(1)
-            self.decoder_forward(B)
-            self._mark("decoder forward + heads")
-            self._pace(2)
-            self.backward(B)
-        finally:
-            self._branches_stay_forked = False
+        stay_forked = not self.aux
+        self._pace(1)
+        self.decoder_forward(B, stay_forked=stay_forked)
+        self._mark("decoder forward + heads")
+        self._pace(2)
+        self.backward(B, stay_forked=stay_forked)
         self._mark("backward")
         self._verify_pipeline(lambda: self._redo_step(B))
 
@@ -163,13 +160,12 @@ class TrainSteps(object):
 
     def _train_step_finish(self, B, allreduce):
         self._bucket_hook = self._overlap_hook(allreduce, B)
-        self._branches_stay_forked = not self.aux
+        stay_forked = not self.aux
         try:
-            self.decoder_forward(B)
+            self.decoder_forward(B, stay_forked=stay_forked)
             self._pace(2)
-            self.backward(B)
+            self.backward(B, stay_forked=stay_forked)
         finally:
-            self._branches_stay_forked = False
             self._bucket_hook = None
         self._verify_pipeline(lambda: self._redo_step(B))
         gs = self._host_call("reduce", lambda: allreduce(self.grads)) if allreduce is not None else 1.0

@@ -593,8 +593,7 @@ def test_batches_on_both_sides_of_the_kstream_gate_on_one_engine(cell):
             sub = {k: v[:B] for k, v in raw.items()}
             _stage(e, sub, B)
             if e is eng:
-                e._cur_B, e._n_side = e.pad16(B), len(e.enc_meta)
-                ks.append(e._kstream_ok(e.enc_notes, e.pad16(B)))
+                ks.append(e._kstream_ok(e.enc_notes, e.pad16(B), len(e.enc_meta)))
             e.train_step(B)
             out.append(e.metrics(B)["loss"])
         e.check_pipeline()
@@ -687,9 +686,8 @@ def test_elbo_trajectory_fresh_epsilon_on_the_benched_schedule(cell):
     st = orc.new_opt_state(p)
     eng = Engine(spec, max_batch=B, dtype="bf16")
     eng.set_params(params)
-    assert eng._pipelined(eng.enc_notes) and eng._pipelined(eng.dec_notes)
-    eng._cur_B, eng._n_side = 16, len(eng.enc_meta)
-    assert eng._kstream_ok(eng.enc_notes, 16)
+    assert eng._pipelined(eng.enc_notes, 16) and eng._pipelined(eng.dec_notes, 16)
+    assert eng._kstream_ok(eng.enc_notes, 16, len(eng.enc_meta))
     worst = {}
     for i in range(steps):
         eps = (np.random.default_rng(1000 + i).standard_normal((B, spec.Z)) * spec.epsilon_std).astype(np.float32)
@@ -787,7 +785,7 @@ def test_one_hot_bottom_layer_written_out_equals_the_indexed_kernel(cell, monkey
         eng.check_pipeline()
         seqs = {k: eng.store[k].clone() for k in ("enc.notes.0.hs", "enc.notes.0.acts", "enc.notes.1.hs", "enc.notes.0.da")}
         if flag == "1":     # the producer's output against the table rows it names
-            Bp = eng._cur_B
+            Bp = eng.pad16(B)
             xp = eng._v("enc.notes.0.xp", spec.T, Bp, spec.GH)
             idx = eng._v("in.x_idx", spec.T, Bp).long()
             table = eng._v("enc.notes.0.table", eng.enc_notes[0].K, spec.GH)

@@ -63,3 +63,18 @@ def test_the_environment_is_only_read_through_the_argument(monkeypatch):
     monkeypatch.setenv("MVAE_DEFER_GRADS_ROWS", "1")
     assert schedule_knobs(_spec(), 256, env={})["defer_grads_rows"] == 32768
     assert schedule_knobs(_spec(), 256)["defer_grads_rows"] == 1
+
+
+def test_a_default_schedule_state_has_nothing_armed():
+    """engine_schedule.py: what the engine holds outside a call - the values Engine.__init__ used to give the loose attributes"""
+    from midi_vae_amd.engine_schedule import CallState, PhaseState
+    call, ph = CallState(), PhaseState()
+    assert {n: getattr(call, n) for n in CallState.__slots__} == dict(
+        deferred_gemms=None, deferred_small=[], deferred_side=None, after_chain=None, tail_streams=[])
+    assert {n: getattr(ph, n) for n in PhaseState.__slots__} == dict(
+        n_side=0, grad_streams=None, prefork=None, hold_side=False, kstream_extra=None, grad_portion_jobs=None, single_slot=0,
+        single_slot_end=3, top_publish=None, last_stack_gate=None)
+    assert CallState().tail_streams is not call.tail_streams      # (no list is shared between instances)
+    assert PhaseState(n_side=2).n_side == 2
+    with pytest.raises(AttributeError):
+        ph.no_such_field = 1

@@ -7,7 +7,7 @@ and a SHA-256 of the case.  Arguments and fields whose DECLARED ctypes type is a
 index of that address's first appearance in the case: which of them coincide stays, the addresses go.  Everything else prints
 verbatim.  Two checkouts that enqueue the same schedule print the same text:
     python tools/launch_trace.py > a.txt        (in each checkout, this file copied in)        diff a.txt b.txt
-``--hashes``: only the per-case lines.  The run ends at the first failing case and is killed after ``--timeout`` seconds."""
+``--hashes``: only the per-case lines; ``--only TEXT``: only the cases whose name contains TEXT.  The run ends at the first failing case and is killed after ``--timeout`` seconds."""
 import argparse, ctypes as C, hashlib, os, signal, struct, sys
 import numpy as np
 import torch
@@ -64,7 +64,7 @@ def trace_lines(rec):
     return lines
 
 
-def inputs(spec, seed=1):
+def inputs(spec, B=B, seed=1):
     rng = np.random.default_rng(seed)
     u8 = lambda hi, *shape: rng.integers(0, hi, shape).astype(np.uint8)
     return dict(x_idx=u8(spec.Dout, B, spec.T), i_idx=u8(spec.ID, B, spec.V), vel=rng.random((B, spec.T)).astype(np.float32),
@@ -84,11 +84,20 @@ class _Hook(object):
         return None
 
 
-def vae_case(kinds, dtype="bf16", knobs=None, training=True, hook=None, **spec_kw):
+def vae_case(kinds, dtype="bf16", knobs=None, training=True, hook=None, batch=B, **spec_kw):
+    """``batch``: windows of the engines' max_batch and of every call but "train96" (a train step of 96 windows on the same engine:
+    with a larger ``batch`` the call's padded batch differs from the engine's)"""
+    B = batch
     spec = ModelSpec(**dict(dict(cell="GRU", H=256, Z=Z, T=T, V=4, C=2, Le=2, Ld=2, lr=1e-3), **spec_kw))
-    raw = inputs(spec)
+    raw = inputs(spec, B)
     train = Engine(spec, max_batch=B, dtype=dtype, seed=0) if training else None
     infer = Engine(spec, max_batch=B, dtype=dtype, seed=0, training=False, share=train)
+
+    def stage(eng, n):
+        sub = {k: v[:n] for k, v in raw.items()}
+        eng.stage_encoder_inputs(sub["x_idx"], sub["i_idx"], sub["vel"], sub["eps"], d_idx=sub["d_idx"])
+        eng.stage_decoder_inputs(n, hist=sub["hist"], add=sub["add"])
+        eng.stage_targets(n, sub["x_idx"], sub["c_idx"], n_idx=sub["n_idx"], sig=sub["sig"])
     for eng in (train, infer):
         if eng is None:
             continue
@@ -96,17 +105,17 @@ def vae_case(kinds, dtype="bf16", knobs=None, training=True, hook=None, **spec_k
         for k, v in (knobs or {}).items():
             assert hasattr(eng, k), k
             setattr(eng, k, v)
-        eng.stage_encoder_inputs(raw["x_idx"], raw["i_idx"], raw["vel"], raw["eps"], d_idx=raw["d_idx"])
-        eng.stage_decoder_inputs(B, hist=raw["hist"], add=raw["add"])
-        eng.stage_targets(B, raw["x_idx"], raw["c_idx"], n_idx=raw["n_idx"], sig=raw["sig"])
+        stage(eng, B)
 
     def decode(**kw):
         infer.stage_decoder_inputs(B, hist=raw["hist"], z=raw["hist"], add=raw["add"])
         infer.decode(B, **kw)
-    calls = {"train": lambda: train.train_step(B, allreduce=hook), "eval": lambda: infer.eval_step(B), "encode": lambda: infer.encode(B),
+    calls = {"train": lambda: train.train_step(B, allreduce=hook), "train96": lambda: train.train_step(96, allreduce=hook), "eval": lambda: infer.eval_step(B), "encode": lambda: infer.encode(B),
              "decode": decode, "decode_argmax": lambda: decode(want_probs=False)}
     for kind in kinds:
-        yield kind, calls[kind], (train if kind == "train" else infer)
+        if kind == "train96":       # (restaged here, outside the recorded call: the generator runs on as the case gets to this kind)
+            stage(train, 96)
+        yield kind, calls[kind], (train if kind.startswith("train") else infer)
 
 
 def classifier_case():
@@ -123,7 +132,14 @@ CASES = [("%s %s" % (cell, tag), lambda cell=cell, knobs=knobs: vae_case(ALL, ce
          for cell in ("LSTM", "GRU")
          for tag, knobs in (("default", {}), ("defer_grads_rows=0", dict(defer_grads_rows=0)), ("phase_multi=False", dict(phase_multi=False)),
                             ("pipeline=False", dict(pipeline=False)), ("phase_max_B=16", dict(phase_max_B=16)),
-                            ("fused_latent=False", dict(fused_latent=False)))]
+                            ("fused_latent=False", dict(fused_latent=False)),
+                            # (defer_grads_rows = 0: the gradient GEMMs run beside the recurrences, K-streaming may be on)
+                            ("phase_multi=False defer_grads_rows=0", dict(phase_multi=False, defer_grads_rows=0)),
+                            ("phase_multi=False defer_grads_rows=0 grad_portions=2", dict(phase_multi=False, defer_grads_rows=0, grad_portions=2)),
+                            ("kstream_grads=False defer_grads_rows=0", dict(kstream_grads=False, defer_grads_rows=0)))]
+# an engine larger than the call: 512 windows (per-queue schedule, ordinary gradient GEMMs), then 96 on the same engine
+CASES += [("%s max_batch=512 defer_grads_rows=0" % cell,
+           lambda cell=cell: vae_case(("train", "train96"), cell=cell, batch=512, knobs=dict(defer_grads_rows=0))) for cell in ("LSTM", "GRU")]
 CASES += [
     ("GRU H=64 f32", lambda: vae_case(ALL, dtype="f32", H=64)),
     ("LSTM comp_notes", lambda: vae_case(ALL, cell="LSTM", comp_notes=True)),
@@ -141,9 +157,12 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--hashes", action="store_true", help="print the per-case SHA-256 lines only")
     ap.add_argument("--timeout", type=int, default=120, help="seconds after which the process is killed (SIGALRM)")
+    ap.add_argument("--only", default="", help="run only the cases whose name contains this text")
     a = ap.parse_args()
     signal.alarm(a.timeout)
     for name, make in CASES:
+        if a.only and a.only not in name:
+            continue
         lines = []
         for kind, call, eng in make():
             for _ in range(3):
