@@ -8,7 +8,8 @@ tensors (n_win, T, 61), c class indices, paths).  With ``load_from_pickle_instea
 ``<name>.pickle`` files under ``pickle_load_path`` (:355-373); after importing MIDI files it writes the same files to
 ``pickle_store_folder`` (:548-571).  That cache format is reproduced here, both ways, so that a dataset imported once with the
 reference feeds ``vae_training.py`` / ``style_classifier_training.py`` unchanged.  Parsing MIDI files themselves (pretty_midi,
-:13-250) is outside the hot path and impossible in this image (pretty_midi is absent): asked for, it raises.  The ARRAY-level end of
+:13-250) is outside the hot path and impossible in this image (pretty_midi is absent): asked for, it raises.  (WRITING them needs no
+library: ``midi_functions.rolls_to_midi``, ``midi_vae_amd.midifile``.)  The ARRAY-level end of
 ``load_rolls`` - silent column, right padding, the split into windows (:256-265, :303-345) - needs no MIDI library and is here as
 ``windows_from_unrolled_rolls``: it is also what turns a decoded song (``process_decoder_outputs``: rows without the silent column,
 all-zero where the model chose silence, ``vae_definition.py:1084-1093``) back into windows the encoder takes.

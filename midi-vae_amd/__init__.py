@@ -9,6 +9,8 @@ through the repo-root shim ``midi_vae_amd.py`` which registers this directory as
   layout    parameter layout of the model (names, shapes, offsets in the flat fp32 buffer)
   hiplib    ctypes binding of the C-ABI library built from csrc/ (include/midivae_hip.h, include/midivae_descriptors.h)
   descriptors  signature vectors and harmonicity of windows, on the device and as a NumPy mirror (reference data_class.py)
+  events    note events of decoded songs, on the device and as a NumPy mirror (reference midi_functions.py, rolls_to_midi)
+  midifile  a Standard MIDI File writer for those notes, and the reader its tests need
   engine    device engine: resident buffers, train step, encode / decode
   model     ``VAE`` facade with the reference's ``create`` / ``fit`` / ``evaluate`` / ``predict`` surface
   synth     synthetic piano-roll windows

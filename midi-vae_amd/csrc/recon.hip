@@ -26,46 +26,11 @@
 
 namespace {
 
-constexpr int BLOCK = 256;
+constexpr int BLOCK = VOICE_BLOCK;
 static_assert(MVAE_RECON_MAX_VOICES == ROLL_MAX_VOICES, "rolls.h refuses more voices than the header's limit");
 constexpr int MAXP = MVAE_RECON_MAX_PITCH, MAX_T = MVAE_RECON_MAX_T;
 constexpr int CHUNK_TICKS = 8;
 constexpr int NCOUNT = 6;          // what a lane counts: columns 0, 1, 2, 5, 6, 7
-
-// the workgroup's windows and this lane's place among them
-struct Place {
-    int V, wpb, w0, nw, wl, v, ticks;
-    bool live;
-    __device__ Place(const mvae_recon_args& a) {
-        V = a.voices;
-        wpb = BLOCK / V;
-        const long long first = (long long)blockIdx.x * wpb;
-        w0 = (int)first;
-        nw = (int)min((long long)wpb, (long long)a.n - first);
-        wl = threadIdx.x / V;
-        v = threadIdx.x - wl * V;
-        ticks = a.T / V;
-        live = wl < nw;
-    }
-};
-
-// rows [tick0 * V, (tick0 + nt) * V) of the workgroup's windows -> tile[tick][wl * V + voice]; every lane of the workgroup calls it
-template <class E>
-__device__ __forceinline__ void stage(const Place& p, const E* src, int64_t stride_t, int64_t stride_w, int tick0, int nt, E* tile) {
-    const int rows = nt * p.V, total = rows * p.nw;
-    const size_t base = (size_t)tick0 * p.V * (size_t)stride_t + (size_t)p.w0 * (size_t)stride_w;
-    if (stride_w == 1) {          // time-major: adjacent lanes, adjacent windows
-        for (int i = threadIdx.x; i < total; i += BLOCK) {
-            const int r = i / p.nw, wl = i - r * p.nw;
-            tile[(r / p.V) * BLOCK + wl * p.V + r % p.V] = src[base + (size_t)r * (size_t)stride_t + (size_t)wl];
-        }
-    } else {                      // adjacent lanes, adjacent rows of a window
-        for (int i = threadIdx.x; i < total; i += BLOCK) {
-            const int wl = i / rows, r = i - wl * rows;
-            tile[(r / p.V) * BLOCK + wl * p.V + r % p.V] = src[base + (size_t)r * (size_t)stride_t + (size_t)wl * (size_t)stride_w];
-        }
-    }
-}
 
 // the same chunk of a tile -> a window-major (n, T) output
 template <class E>

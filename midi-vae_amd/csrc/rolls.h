@@ -1,4 +1,4 @@
-// What the kernels over decoded piano-roll windows share (descriptors.hip, sweep.hip, recon.hip): which row sounds, the exact
+// What the kernels over decoded piano-roll windows share (descriptors.hip, sweep.hip, recon.hip, events.hip): which row sounds, the exact
 // integer statistics of a list, the rows of a chunk of ticks with one lane per window, one row of the velocity post-rule, and the
 // refusals common to the three entry points.  Row t of a window is voice t % V of tick t // V.
 #pragma once
@@ -85,6 +85,46 @@ struct Rows {
     __device__ int idx(int tick0, int r) const { return STAGED ? ti[r * TILE_LD + lane] : a.idx[at(tick0, r)]; }
     __device__ float vel(int tick0, int r) const { return STAGED ? tv[r * TILE_LD + lane] : a.vel[at(tick0, r)]; }
 };
+
+// The kernels with ONE LANE PER (WINDOW, VOICE) (recon.hip, events.hip): the voices of a window in adjacent lanes, VOICE_BLOCK lanes a
+// workgroup hold VOICE_BLOCK / voices windows; rows travel through LDS tiles [tick][lane].
+constexpr int VOICE_BLOCK = 256;
+
+// the workgroup's windows and this lane's place among them
+struct Place {
+    int V, wpb, w0, nw, wl, v, ticks;
+    bool live;
+    template <class Args>
+    __device__ Place(const Args& a) {
+        V = a.voices;
+        wpb = VOICE_BLOCK / V;
+        const long long first = (long long)blockIdx.x * wpb;
+        w0 = (int)first;
+        nw = (int)min((long long)wpb, (long long)a.n - first);
+        wl = threadIdx.x / V;
+        v = threadIdx.x - wl * V;
+        ticks = a.T / V;
+        live = wl < nw;
+    }
+};
+
+// rows [tick0 * V, (tick0 + nt) * V) of the workgroup's windows -> tile[tick][wl * V + voice]; every lane of the workgroup calls it
+template <class E>
+__device__ __forceinline__ void stage(const Place& p, const E* src, int64_t stride_t, int64_t stride_w, int tick0, int nt, E* tile) {
+    const int rows = nt * p.V, total = rows * p.nw;
+    const size_t base = (size_t)tick0 * p.V * (size_t)stride_t + (size_t)p.w0 * (size_t)stride_w;
+    if (stride_w == 1) {          // time-major: adjacent lanes, adjacent windows
+        for (int i = threadIdx.x; i < total; i += VOICE_BLOCK) {
+            const int r = i / p.nw, wl = i - r * p.nw;
+            tile[(r / p.V) * VOICE_BLOCK + wl * p.V + r % p.V] = src[base + (size_t)r * (size_t)stride_t + (size_t)wl];
+        }
+    } else {                      // adjacent lanes, adjacent rows of a window
+        for (int i = threadIdx.x; i < total; i += VOICE_BLOCK) {
+            const int wl = i / rows, r = i - wl * rows;
+            tile[(r / p.V) * VOICE_BLOCK + wl * p.V + r % p.V] = src[base + (size_t)r * (size_t)stride_t + (size_t)wl * (size_t)stride_w];
+        }
+    }
+}
 
 // One row of the velocity post-rule (reference vae_definition.py:1156-1190) for one voice: ``snd`` whether the row sounds, ``x`` its
 // index, ``v0`` its velocity (0 on a row that does not sound); ``pp`` / ``pv`` the voice's previous pitch (-1: none) and the last

@@ -171,6 +171,22 @@ RECON_SIGNATURES = {
     "mvae_recon_songs": (_i32, [C.POINTER(ReconArgs), _vp]),
 }
 
+
+class EventsArgs(C.Structure):
+    """mvae_events_args of include/midivae_events.h"""
+    _fields_ = [("idx", _vp), ("stride_t", _i64), ("stride_w", _i64), ("vel", _vp), ("held", _vp), ("song", _vp), ("n", _i32), ("T", _i32),
+                ("voices", _i32), ("silent", _i32), ("n_pitch", _i32), ("n_songs", _i32), ("smallest_note", _i32), ("pitch_base", _i32),
+                ("close_at_end", _i32), ("capacity", _i32), ("threshold", C.c_double), ("workspace", _vp), ("records", _vp),
+                ("offsets", _vp), ("total", _vp)]
+
+
+EVENTS_ABI_VERSION = 1
+# the fifth header, include/midivae_events.h (versioned on its own, like the second, third and fourth)
+EVENTS_SIGNATURES = {
+    "mvae_events_abi_version": (_i32, []),
+    "mvae_note_events": (_i32, [C.POINTER(EventsArgs), _vp]),
+}
+
 # name -> (restype, argtypes); every symbol include/midivae_hip.h declares
 SIGNATURES = {
     "mvae_abi_version": (_i32, []),
@@ -239,11 +255,12 @@ SIGNATURES = {
     "mvae_host_rows_to_tm_f32": (_i32, [_vp, _i32, _i64, _i32, _i64, _i64, _f32, _vp, _i32]),
 }
 
-# the four headers under include/: (what its message calls it, version symbol, version constant, signatures)
+# the five headers under include/: (what its message calls it, version symbol, version constant, signatures)
 HEADERS = (("", "mvae_abi_version", ABI_VERSION, SIGNATURES),
            ("descriptor ", "mvae_desc_abi_version", DESC_ABI_VERSION, DESC_SIGNATURES),
            ("sweep ", "mvae_sweep_abi_version", SWEEP_ABI_VERSION, SWEEP_SIGNATURES),
-           ("reconstruction ", "mvae_recon_abi_version", RECON_ABI_VERSION, RECON_SIGNATURES))
+           ("reconstruction ", "mvae_recon_abi_version", RECON_ABI_VERSION, RECON_SIGNATURES),
+           ("note events ", "mvae_events_abi_version", EVENTS_ABI_VERSION, EVENTS_SIGNATURES))
 
 _lib = None
 

@@ -646,7 +646,8 @@ class Decoder(_ModelView):
             res["velocity"] = got["velocity"].reshape(n, Z, K, sp.T)
         return res
 
-    def predict_songs(self, xs, batch_size=32, sample_method="argmax", temperature=None, seed=None, uniforms=None, originals=None):
+    def predict_songs(self, xs, batch_size=32, sample_method="argmax", temperature=None, seed=None, uniforms=None, originals=None,
+                      note_events=False, close_at_end=False):
         """Decode whole songs and finish them on the device: ``xs`` is one decoder input list per song, as predict_indices takes them
         (``prepare_decoder_input`` with the song's own history); all songs run as ONE chip-filling decode.  Every engine batch's note,
         velocity and held buffers are copied on the device into window-major rolls of the whole run, and after the last batch
@@ -659,13 +660,22 @@ class Decoder(_ModelView):
         refused like packers.process_decoder_indices refuses it.  One dict per song: ``notes`` (n_i, T) uint8, ``velocity``
         (n_i, T) float32 after the rules, ``starts`` (n_i, T) uint8 (0 = a note starts; all 1 for a model with neither a velocity
         nor a held-notes head), ``instr`` (n_i, max_voices) uint8 where the model has the head, ``counts`` (n_i, 8) int32
-        (reconstruction.COUNTS) and, with ``originals``, ``metrics``.  Other arguments as predict_note_indices."""
+        (reconstruction.COUNTS) and, with ``originals``, ``metrics``.  ``note_events``: mvae_note_events (midi_vae_amd.events) runs
+        right behind mvae_recon_songs on the same device rolls - the velocities after the rules and the note starts (the held head's
+        index where the model has one) are what the reference hands rolls_to_midi as V_pred and D_pred - and every song's dict gains
+        ``events``, its notes as an events.RECORD array sorted by (voice, start) (``close_at_end``: a note still sounding on the
+        song's last row is closed there instead of dropped), and, where the model has the instrument head, ``programs``: the
+        per-voice vote over the song's windows (events.vote_for_programs); the offsets and the records they count are two more
+        device-to-host reads.  Other arguments as predict_note_indices."""
         import torch
         from . import packers
         from . import reconstruction as rec
         from .rolls import as_rolls
         (s, p), sp = self._analysis(rec), self._s.spec
         packers.refuse_meta_without_instrument(s)
+        if note_events:
+            from . import events as ev
+            _, ep = self._analysis(ev)
         xs = [_as_list(x) for x in xs]
         if not xs:
             return []
@@ -692,10 +702,18 @@ class Decoder(_ModelView):
             first = torch.from_numpy(rec.first_windows(lengths, n)).to(dev)
             outs = rec.run_on_device(rolls["notes"], rolls.get("velocity"), rolls.get("held"), None if orig is None else torch.from_numpy(orig).to(dev),
                                      first, p)
+            if note_events:
+                ev._check(sp.T, ep, n)
+                song = torch.from_numpy(ev.song_ordinals(lengths, n)).to(dev)
+                table = ev.run_on_device(rolls["notes"], outs[0], outs[1], song, len(lengths), ep, close_at_end)
             velocity, starts, counts = (t.cpu().numpy() for t in outs)
             notes = rolls["notes"].cpu().numpy()
             instr = rolls["instr"].cpu().numpy() if "instr" in rolls else None
         metrics = rec.song_metrics(counts, lengths, sp.T, s) if orig is not None else None
+        if note_events:
+            with torch.cuda.device(dev):
+                song_events = ev.split_songs(*ev.read_back(table[0], table[1]), sp.V)
+            programs = ev.vote_for_programs(instr, lengths, s) if instr is not None else None
         res, lo = [], 0
         for i, m in enumerate(lengths):
             d = dict(notes=notes[lo:lo + m], velocity=velocity[lo:lo + m], starts=starts[lo:lo + m], counts=counts[lo:lo + m])
@@ -703,6 +721,10 @@ class Decoder(_ModelView):
                 d["instr"] = instr[lo:lo + m]
             if metrics is not None:
                 d["metrics"] = metrics[i]
+            if note_events:
+                d["events"] = song_events[i]
+                if programs is not None:
+                    d["programs"] = programs[i]
             res.append(d)
             lo += m
         return res
