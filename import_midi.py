@@ -7,9 +7,10 @@ reference import_midi.py:352-574 ``import_midi_from_folder(folder)`` returns six
 tensors (n_win, T, 61), c class indices, paths).  With ``load_from_pickle_instead_of_midi`` it reads them from sixteen
 ``<name>.pickle`` files under ``pickle_load_path`` (:355-373); after importing MIDI files it writes the same files to
 ``pickle_store_folder`` (:548-571).  That cache format is reproduced here, both ways, so that a dataset imported once with the
-reference feeds ``vae_training.py`` / ``style_classifier_training.py`` unchanged.  Parsing MIDI files themselves (pretty_midi,
-:13-250) is outside the hot path and impossible in this image (pretty_midi is absent): asked for, it raises.  (WRITING them needs no
-library: ``midi_functions.rolls_to_midi``, ``midi_vae_amd.midifile``.)  The ARRAY-level end of
+reference feeds ``vae_training.py`` / ``style_classifier_training.py`` unchanged.  READING MIDI files is ``load_rolls`` and
+``import_folder`` below, which forward to ``midi_vae_amd.midi_import`` (a reader of its own, not pretty_midi's - see there - and the
+rolls built on the device); ``import_midi_from_folder`` itself keeps its refusal and names ``import_folder``.  (WRITING them:
+``midi_functions.rolls_to_midi``, ``midi_vae_amd.midifile``.)  The ARRAY-level end of
 ``load_rolls`` - silent column, right padding, the split into windows (:256-265, :303-345) - needs no MIDI library and is here as
 ``windows_from_unrolled_rolls``: it is also what turns a decoded song (``process_decoder_outputs``: rows without the silent column,
 all-zero where the model chose silence, ``vae_definition.py:1084-1093``) back into windows the encoder takes.
@@ -95,6 +96,19 @@ def import_midi_from_folder(folder):
     if s.get("load_from_pickle_instead_of_midi"):
         return load_pickle_cache(s["pickle_load_path"])
     raise NotImplementedError(
-        "importing MIDI files (%r) needs pretty_midi, which this image does not have, and is outside this repo's scope (SURVEY "
-        "section 2: MIDI import / export); import the dataset once with the reference (save_imported_midi_as_pickle = True) and set "
-        "load_from_pickle_instead_of_midi = True / pickle_load_path - or pass --pickle-dir to vae_training.py" % (folder,))
+        "import_midi_from_folder(%r) would need pretty_midi, whose parser this repo does not claim to reproduce; call import_folder "
+        "(this module, or midi_vae_amd.midi_import) for the same sixteen lists from this repo's own reader - or import the dataset once "
+        "with the reference (save_imported_midi_as_pickle = True) and set load_from_pickle_instead_of_midi = True / pickle_load_path, "
+        "or pass --midi-dir / --pickle-dir to vae_training.py" % (folder,))
+
+
+def load_rolls(path, name, s=None, device=False):
+    """reference import_midi.py:13-350 on this repo's own reader: midi_vae_amd.midi_import.load_rolls"""
+    from midi_vae_amd import midi_import
+    return midi_import.load_rolls(path, name, s, device)
+
+
+def import_folder(folder, s=None, device=True):
+    """reference import_midi.py:375-574, the sixteen lists: midi_vae_amd.midi_import.import_folder"""
+    from midi_vae_amd import midi_import
+    return midi_import.import_folder(folder, s, device)

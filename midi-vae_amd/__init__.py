@@ -11,6 +11,7 @@ through the repo-root shim ``midi_vae_amd.py`` which registers this directory as
   descriptors  signature vectors and harmonicity of windows, on the device and as a NumPy mirror (reference data_class.py)
   events    note events of decoded songs, on the device and as a NumPy mirror (reference midi_functions.py, rolls_to_midi)
   midifile  a Standard MIDI File writer for those notes, and the reader its tests need
+  midi_import  MIDI files into training windows: reader, tick quantisation, rolls from notes on the device (reference import_midi.py)
   engine    device engine: resident buffers, train step, encode / decode
   model     ``VAE`` facade with the reference's ``create`` / ``fit`` / ``evaluate`` / ``predict`` surface
   synth     synthetic piano-roll windows

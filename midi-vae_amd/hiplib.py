@@ -187,6 +187,22 @@ EVENTS_SIGNATURES = {
     "mvae_note_events": (_i32, [C.POINTER(EventsArgs), _vp]),
 }
 
+class ImportArgs(C.Structure):
+    """mvae_import_args of include/midivae_import.h"""
+    _fields_ = [("notes", _vp), ("note_off", _vp), ("track_off", _vp), ("ticks", _vp), ("win_off", _vp), ("n_songs", _i32),
+                ("n_notes", _i32), ("n_tracks", _i32), ("n_windows", _i32), ("T", _i32), ("voices", _i32), ("max_per_track", _i32),
+                ("pitch_base", _i32), ("n_pitch", _i32), ("silent", _i32), ("cells", _i64), ("stride_t", _i64), ("stride_w", _i64),
+                ("threshold", C.c_double), ("workspace", _vp), ("idx", _vp), ("held", _vp), ("vel_raw", _vp), ("vel", _vp),
+                ("concurrent", _vp), ("slots", _vp), ("slot_voice", _vp)]
+
+
+IMPORT_ABI_VERSION = 1
+# the sixth header, include/midivae_import.h (versioned on its own, like the second to fifth)
+IMPORT_SIGNATURES = {
+    "mvae_import_abi_version": (_i32, []),
+    "mvae_rolls_from_notes": (_i32, [C.POINTER(ImportArgs), _vp]),
+}
+
 # name -> (restype, argtypes); every symbol include/midivae_hip.h declares
 SIGNATURES = {
     "mvae_abi_version": (_i32, []),
@@ -255,12 +271,13 @@ SIGNATURES = {
     "mvae_host_rows_to_tm_f32": (_i32, [_vp, _i32, _i64, _i32, _i64, _i64, _f32, _vp, _i32]),
 }
 
-# the five headers under include/: (what its message calls it, version symbol, version constant, signatures)
+# the six headers under include/: (what its message calls it, version symbol, version constant, signatures)
 HEADERS = (("", "mvae_abi_version", ABI_VERSION, SIGNATURES),
            ("descriptor ", "mvae_desc_abi_version", DESC_ABI_VERSION, DESC_SIGNATURES),
            ("sweep ", "mvae_sweep_abi_version", SWEEP_ABI_VERSION, SWEEP_SIGNATURES),
            ("reconstruction ", "mvae_recon_abi_version", RECON_ABI_VERSION, RECON_SIGNATURES),
-           ("note events ", "mvae_events_abi_version", EVENTS_ABI_VERSION, EVENTS_SIGNATURES))
+           ("note events ", "mvae_events_abi_version", EVENTS_ABI_VERSION, EVENTS_SIGNATURES),
+           ("import ", "mvae_import_abi_version", IMPORT_ABI_VERSION, IMPORT_SIGNATURES))
 
 _lib = None
 

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Training entrypoint with the shape of the reference's three classifier scripts (pitch_classifier.py, velocity_classifier.py,
 instrument_classifier.py: model :89-103, per-song fit loop :223-245, test() with the confusion matrix :117-160) on the MI355X
-engine.  The reference reads MIDI folders (import_midi.py, out of scope); songs here are synthetic piano-roll windows whose
-statistics depend on the class, so the classifiers have something to learn.
+engine.  Songs are synthetic piano-roll windows whose statistics depend on the class, so the classifiers have something to learn,
+or - ``--midi-dir`` - the MIDI files of a folder with class-named subfolders (import_midi.import_folder).
 
-    python style_classifier_training.py --kind pitch|velocity|instrument [--epochs 5] [--songs 12]
+    python style_classifier_training.py --kind pitch|velocity|instrument [--epochs 5] [--songs 12] [--midi-dir DIR]
 """
 import argparse
 import time
@@ -33,6 +33,12 @@ def synthetic_songs(n_songs, s, seed, kind):
     return songs
 
 
+def songs_from_midi_dir(folder, s):
+    """(train, test) song dicts from the MIDI files under ``folder``, as vae_training.songs_from_midi_dir makes them"""
+    import vae_training
+    return vae_training.songs_from_midi_dir(folder, s)
+
+
 def sample(song, kind, num_classes):
     """(inputs, targets) of one song, built as the reference scripts build them"""
     if kind == "pitch":
@@ -55,6 +61,7 @@ def main():
     ap.add_argument("--batch-size", type=int, default=512)                  # the scripts' batch_size
     ap.add_argument("--learning-rate", type=float, default=2e-5)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
+    ap.add_argument("--midi-dir", default="", help="a folder of .mid / .midi files in class-named subfolders instead of synthetic songs")
     args = ap.parse_args()
     s = vars(settings)
     nc = s["num_classes"]
@@ -62,8 +69,11 @@ def main():
     model = StyleClassifier(args.kind, input_dim=input_dim, num_classes=nc, lstm_size=256, num_layers=2,
                             learning_rate=args.learning_rate, optimizer="Adam", compute_dtype=args.dtype)
     print(model.summary())
-    train = synthetic_songs(args.songs, s, 1, args.kind)
-    test = synthetic_songs(args.test_songs, s, 99, args.kind)
+    if args.midi_dir:
+        train, test = songs_from_midi_dir(args.midi_dir, s)
+    else:
+        train = synthetic_songs(args.songs, s, 1, args.kind)
+        test = synthetic_songs(args.test_songs, s, 99, args.kind)
     for e in range(1, args.epochs + 1):
         t0 = time.time()
         order = np.random.permutation(len(train))

@@ -3,10 +3,10 @@
 :728-815 per-song fit loop with the history pre-pass, :243-351 test(), :817-961 metric bookkeeping with KL derived by
 subtraction, :966-978 checkpoints) on the MI355X engine.
 
-The reference imports MIDI files with pretty_midi (import_midi.py), which is outside this repo's scope: songs here are
-synthetic piano-roll windows with the same tensor layout (midi_vae_amd/synth.py), or ``--pickle`` pointing at arrays
-saved by a user's own importer (an ``.npz`` with X, C, I, V per song).  Plots / tikz / the ~30 per-epoch pickles of
-the reference are not reproduced.
+Songs are synthetic piano-roll windows with the reference's tensor layout (midi_vae_amd/synth.py), or ``--midi-dir`` a folder of
+MIDI files in class-named subfolders (import_midi.import_folder: this repo's own reader, the rolls built on the device), or
+``--pickle-dir`` the dataset cache the reference - or import_folder - wrote.  Plots / tikz / the ~30 per-epoch pickles of the
+reference are not reproduced.
 
     python vae_training.py --epochs 3 --songs 6                         (single GPU)
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 vae_training.py --epochs 3   (DP: every
@@ -41,7 +41,26 @@ def synthetic_songs(n_songs, s, seed):
 def songs_from_pickle_cache(path, s):
     """(train, test) song dicts from the reference's dataset cache (import_midi.load_pickle_cache; reference vae_training.py:142)"""
     import import_midi
-    (V_tr, V_te, D_tr, D_te, _, _, I_tr, I_te, Y_tr, Y_te, X_tr, X_te, c_tr, c_te, _, _) = import_midi.load_pickle_cache(path)
+    return songs_from_lists(import_midi.load_pickle_cache(path), s)
+
+
+def songs_from_midi_dir(folder, s, device=True):
+    """(train, test) song dicts from the MIDI files under ``folder`` (import_midi.import_folder; reference vae_training.py:142).  The
+    reference sets the silent bit on EVERY row of a song that needs no padding (``X[-0:, -1] = 1``); the lists keep that, the songs
+    handed to the engine do not: a row with a note loses the bit again, so every row stays one-hot."""
+    import import_midi
+    train, test = songs_from_lists(import_midi.import_folder(folder if folder.endswith("/") else folder + "/", s, device), s)
+    if s["include_silent_note"]:
+        for song in train + test:
+            for k in ("X", "Y"):
+                a = song[k] = song[k].copy()
+                a[..., -1] = np.where(a[..., :-1].sum(-1) > 0, 0.0, a[..., -1])
+    return train, test
+
+
+def songs_from_lists(lists, s):
+    """(train, test) song dicts from the reference's sixteen lists"""
+    (V_tr, V_te, D_tr, D_te, _, _, I_tr, I_te, Y_tr, Y_te, X_tr, X_te, c_tr, c_te, _, _) = lists
 
     def songs(X, Y, C, I, V, D):
         return [dict(X=np.asarray(x), Y=np.asarray(y), C=int(c), I=np.asarray(i), V=np.asarray(v), D=np.asarray(d),
@@ -149,6 +168,8 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend when WORLD_SIZE > 1")
     ap.add_argument("--pickle-dir", default="", help="a dataset cache written by the reference (import_midi.py:548-571: V_train.pickle ... "
                     "test_paths.pickle) instead of synthetic songs")
+    ap.add_argument("--midi-dir", default="", help="a folder of .mid / .midi files, a file's class being the first of settings.classes its "
+                    "path names (import_midi.import_folder), instead of synthetic songs")
     ap.add_argument("--batched-test", action="store_true", help="run the test pass of all songs as one chip-filling per-window "
                     "pass (autoencoder.evaluate_songs) instead of one evaluate call per song")
     ap.add_argument("--signatures", default="zeros", choices=["zeros", "host", "device"], help="the songs' signature vectors S (target of "
@@ -179,7 +200,9 @@ def main():
     if s["load_previous_checkpoint"]:
         for view, name in ((model.autoencoder, "autoencoder"), (model.encoder, "encoder"), (model.decoder, "decoder")):
             view.load_weights(s["previous_checkpoint_path"] + name + "Epoch" + str(s["previous_epoch"]) + ".pickle", by_name=False)
-    if args.pickle_dir:
+    if args.midi_dir:
+        train, test = songs_from_midi_dir(args.midi_dir, s)
+    elif args.pickle_dir:
         train, test = songs_from_pickle_cache(args.pickle_dir, s)
     else:
         train = synthetic_songs(args.songs, s, seed=1)         # the SAME songs on every rank (sharded inside fit)
