@@ -85,6 +85,25 @@ class ClassifierEngine(Engine):
             self._up("in.rw", rw, torch.float32)
         return B
 
+    def stage_device(self, x_tm, B):
+        """``stage`` without targets from device memory: ``x_tm`` is a time-major (T, >= B) device view - uint8 indices or float32
+        values, e.g. the transpose of window-major rolls a decode left behind - whose first ``B`` columns are copied into the input
+        buffer; the pad columns are zeroed as ``stage`` zeroes them.  Plain copies on the current stream, nothing crosses to the host"""
+        s = self.spec
+        name, dt = ("in.x_idx", torch.uint8) if s.xmode == "index" else ("in.x_val", torch.float32)
+        if not isinstance(x_tm, torch.Tensor) or x_tm.device != self.store[name].device:
+            raise ValueError("stage_device takes a tensor on %s" % (self.store[name].device,))
+        if x_tm.dtype != dt or x_tm.dim() != 2 or x_tm.shape[0] != s.T or not 0 < B <= x_tm.shape[1]:
+            raise ValueError("stage_device: expected a (%d, >= %d) %s view, got %r %s" % (s.T, B, dt, tuple(x_tm.shape), x_tm.dtype))
+        Bp = self.pad16(B)
+        dst = self._v(name, s.T, Bp)
+        dst[:, :B].copy_(x_tm[:, :B])
+        if Bp > B:
+            dst[:, B:].zero_()
+        self._have_targets = False
+        self.norm_B = float(B)
+        return B
+
     # ---- forward / backward ------------------------------------------------------------------------------------
     def forward(self, B, want_probs=False, verify=None):
         """``verify``: check the first time-pipelined use of a forward-only call (evaluate / predict) as Engine.encode does; a
@@ -145,7 +164,11 @@ class ClassifierEngine(Engine):
         return OrderedDict(loss=v[S_LOSS], acc=v[S_HITS] / B)
 
     def probs(self, B):
-        return self._v("out.cls_p", self.pad16(B), self.spec.C)[:B].cpu().numpy()
+        return self.probs_device(B).cpu().numpy()
+
+    def probs_device(self, B):
+        """the (B, C) float32 probabilities of the last forward(want_probs=True), a view of the engine's own buffer"""
+        return self._v("out.cls_p", self.pad16(B), self.spec.C)[:B]
 
 
 class StyleClassifier(object):
@@ -241,17 +264,34 @@ class StyleClassifier(object):
         m = eng.read_accumulated(n)
         return [m["loss"], m["acc"]]
 
-    def predict(self, X, batch_size=32, verbose=0):
-        x = self._inputs(X)
+    def _device_inputs(self, X):
+        """a window-major (n, T) device roll - uint8 note indices, (n, V) instrument bytes, float32 velocities - as it is"""
+        want = torch.float32 if self.xmode == "scalar" else torch.uint8
+        if X.dim() != 2 or X.dtype != want:
+            raise ValueError("a device roll for the %s classifier is a 2-D %s tensor, got %r %s" % (self.kind, want, tuple(X.shape), X.dtype))
+        return X
+
+    def predict(self, X, batch_size=32, verbose=0, as_device=False):
+        """``X`` as fit takes it, or a window-major device tensor: (n, T) uint8 note indices / (n, V) uint8 instrument bytes / (n, T)
+        float32 velocities - what a decode leaves behind; a device roll is copied into the engine's input buffer on the device
+        (ClassifierEngine.stage_device).  ``as_device``: the (n, C) float32 probabilities stay a device tensor - one copy out of
+        the engine's buffer per engine batch, nothing is read back"""
+        on_device = isinstance(X, torch.Tensor) and X.is_cuda
+        x = self._device_inputs(X) if on_device else self._inputs(X)
         n, T = x.shape
         eng = self._engine(T, batch_size)
-        out = []
+        out = torch.empty((n, self.cfg["C"]), dtype=torch.float32, device=eng.device) if as_device else []
         for lo in range(0, n, batch_size):
             hi = min(n, lo + batch_size)
-            B = eng.stage(x[lo:hi], None)
+            B = eng.stage_device(x[lo:hi].t(), hi - lo) if on_device else eng.stage(x[lo:hi], None)
             eng.forward(B, want_probs=True, verify=True)
-            out.append(eng.probs(B))
+            if as_device:
+                out[lo:hi].copy_(eng.probs_device(B))
+            else:
+                out.append(eng.probs(B))
         eng.check_pipeline()
+        if as_device:
+            return out
         return np.concatenate(out, 0) if out else np.zeros((0, self.cfg["C"]), np.float32)
 
     def reset_states(self):

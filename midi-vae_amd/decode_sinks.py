@@ -88,6 +88,37 @@ class SweepStatistics(Sink):
         return res
 
 
+class JudgedSweepStatistics(SweepStatistics):
+    """latent_sweep with ``judges`` (style.Judges): SweepStatistics, and behind every engine batch the three style classifiers read
+    the decode's note and instrument buffers and the velocities after the rules (a second launch of the statistics kernel that
+    only writes them) on the device; the class-0 probabilities of the whole run stay there until ``result`` reads them once.
+    ``style`` (n, 3) float32, a NaN column where the model lacks the head or the judge is absent"""
+
+    def batch(self, eng, lo, hi, views):
+        import torch
+        SweepStatistics.batch(self, eng, lo, hi, views)
+        B, rows, vel = hi - lo, views["notes"], views.get("velocity")
+        after = None
+        with torch.cuda.device(rows.device):
+            if vel is not None:
+                after = torch.empty((B, rows.shape[0]), dtype=torch.float32, device=rows.device)
+                sweep.enqueue(rows.data_ptr(), vel.data_ptr(), rows.stride(0), rows.stride(1), B, rows.shape[0], self.p, None, after,
+                              torch.cuda.current_stream().cuda_stream)
+            instr = views["instr"][:, :B].t() if "instr" in views else None
+            tables = self.judges.probabilities(rows[:, :B].t(), after, instr, self.batch_size)
+            col = torch.full((B, 3), float("nan"), dtype=torch.float32, device=rows.device)
+            for j, t in enumerate(tables):
+                if t is not None:
+                    col[:, j].copy_(t[:, 0])
+        self.style.append(col)
+
+    def result(self):
+        import torch
+        res = SweepStatistics.result(self)
+        res["style"] = torch.cat(self.style, 0).cpu().numpy() if self.style else np.zeros((0, 3), np.float32)
+        return res
+
+
 class SongRolls(Sink):
     """predict_songs: every engine batch's buffers are copied - transposed, on the device - into window-major rolls of the
     whole run (a song may straddle engine batches); nothing is read back.  dict of device tensors ``notes`` (n, T) uint8 and, as far as

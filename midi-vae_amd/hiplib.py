@@ -203,6 +203,22 @@ IMPORT_SIGNATURES = {
     "mvae_rolls_from_notes": (_i32, [C.POINTER(ImportArgs), _vp]),
 }
 
+
+class StyleArgs(C.Structure):
+    """mvae_style_args of include/midivae_style.h"""
+    _fields_ = [("p_pitch", _vp), ("p_vel", _vp), ("p_instr", _vp), ("instr_row", _vp), ("cls", _vp), ("group_off", _vp), ("n", _i32),
+                ("C", _i32), ("n_groups", _i32), ("n_instr_rows", _i32), ("ld_pitch", _i32), ("ld_vel", _i32), ("ld_instr", _i32),
+                ("ld_ens", _i32), ("ld_table", _i32), ("reserved", _i32), ("weights", C.c_double * 3), ("ens_out", _vp),
+                ("pred_out", _vp), ("table_out", _vp), ("confusion_out", _vp)]
+
+
+STYLE_ABI_VERSION = 1
+# the seventh header, include/midivae_style.h (versioned on its own, like the second to sixth)
+STYLE_SIGNATURES = {
+    "mvae_style_abi_version": (_i32, []),
+    "mvae_style_scores": (_i32, [C.POINTER(StyleArgs), _vp]),
+}
+
 # name -> (restype, argtypes); every symbol include/midivae_hip.h declares
 SIGNATURES = {
     "mvae_abi_version": (_i32, []),
@@ -271,13 +287,14 @@ SIGNATURES = {
     "mvae_host_rows_to_tm_f32": (_i32, [_vp, _i32, _i64, _i32, _i64, _i64, _f32, _vp, _i32]),
 }
 
-# the six headers under include/: (what its message calls it, version symbol, version constant, signatures)
+# the seven headers under include/: (what its message calls it, version symbol, version constant, signatures)
 HEADERS = (("", "mvae_abi_version", ABI_VERSION, SIGNATURES),
            ("descriptor ", "mvae_desc_abi_version", DESC_ABI_VERSION, DESC_SIGNATURES),
            ("sweep ", "mvae_sweep_abi_version", SWEEP_ABI_VERSION, SWEEP_SIGNATURES),
            ("reconstruction ", "mvae_recon_abi_version", RECON_ABI_VERSION, RECON_SIGNATURES),
            ("note events ", "mvae_events_abi_version", EVENTS_ABI_VERSION, EVENTS_SIGNATURES),
-           ("import ", "mvae_import_abi_version", IMPORT_ABI_VERSION, IMPORT_SIGNATURES))
+           ("import ", "mvae_import_abi_version", IMPORT_ABI_VERSION, IMPORT_SIGNATURES),
+           ("style ", "mvae_style_abi_version", STYLE_ABI_VERSION, STYLE_SIGNATURES))
 
 _lib = None
 

@@ -611,7 +611,7 @@ class Decoder(_ModelView):
                                              np.zeros(zs.shape))
 
     def latent_sweep(self, z, range_end_in_stds=1.0, sigma=1.0, evaluations_per_dimension=5, positive_and_negative=True,
-                     batch_size=32, sample_method="argmax", temperature=None, seed=None, return_rolls=False):
+                     batch_size=32, sample_method="argmax", temperature=None, seed=None, return_rolls=False, judges=None):
         """The reference's latent_sweep_over_all_dimensions (vae_evaluation.py:1123-1213) without its plots: for every sample of
         ``z`` (n, Z) and every latent dimension, decode the K windows in which that one coordinate takes the values of
         sweep.sweep_values(...), and rank the dimensions by how the windows' pitch, velocity and instrument statistics move.  The
@@ -621,7 +621,11 @@ class Decoder(_ModelView):
         ``decoder.sample_settings`` (None: the defaults of config.build_settings()).  dict: ``table`` (n, Z, K, 22) (columns:
         sweep.COLUMNS), ``programs`` (n, Z, K, max_voices), ``values`` (K,), ``summaries[sample][dim]`` name -> (strength,
         probability), ``influence`` name -> (Z,) array, ``most_peaked`` / ``overall_best`` name -> dimension; with ``return_rolls``
-        also ``notes`` (n, Z, K, T) uint8 and ``velocity`` (n, Z, K, T) float32 after the rules."""
+        also ``notes`` (n, Z, K, T) uint8 and ``velocity`` (n, Z, K, T) float32 after the rules.  ``judges`` (style.Judges): behind
+        every engine batch the three style classifiers read the decode's buffers on the device, ``style`` (n, Z, K, 3) holds the
+        class-0 probability the pitch, velocity and instrument judge give every window (NaN: no such head or judge) and the
+        summaries gain the reference's ``mean_pitchstyle_*``, ``mean_velocitystyle_*`` and ``mean_instrumentstyle_*`` keys
+        (:1035-1039, :1089-1093, :1105-1109); one more device-to-host read for the whole run."""
         from . import packers
         from . import sweep as sweep_mod
         (s, p), sp = self._analysis(sweep_mod), self._s.spec
@@ -631,23 +635,29 @@ class Decoder(_ModelView):
         n, Z, K = z.shape[0], sp.Z, len(values)
         if n == 0:
             raise ValueError("z holds no sample")
-        got = self._sampled_run(x, batch_size, sinks.SweepStatistics(p=p, T=sp.T, return_rolls=return_rolls), sample_method, temperature,
-                                seed, None)
+        if judges is None:
+            sink = sinks.SweepStatistics(p=p, T=sp.T, return_rolls=return_rolls)
+        else:
+            sink = sinks.JudgedSweepStatistics(p=p, T=sp.T, return_rolls=return_rolls, judges=judges, batch_size=batch_size, style=[])
+        got = self._sampled_run(x, batch_size, sink, sample_method, temperature, seed, None)
         table = got["table"].reshape(n, Z, K, sweep_mod.N_COLUMNS)
         if got["instr"] is not None:
             programs = sweep_mod.programs_of(got["instr"], packers._g(s, "instrument_attach_method")).reshape(n, Z, K, sp.V)
         else:          # the reference's default I: all piano
             programs = np.zeros((n, Z, K, sp.V), np.int64)
-        summaries, infl, peaked, best = sweep_mod.summarize_sweep(table, programs)
+        style = got["style"].reshape(n, Z, K, 3) if judges is not None else None
+        summaries, infl, peaked, best = sweep_mod.summarize_sweep(table, programs, style=style)
         res = dict(table=table, programs=programs, values=values, summaries=summaries, influence=infl, most_peaked=peaked,
                    overall_best=best)
+        if style is not None:
+            res["style"] = style
         if return_rolls:
             res["notes"] = got["notes"].reshape(n, Z, K, sp.T)
             res["velocity"] = got["velocity"].reshape(n, Z, K, sp.T)
         return res
 
     def predict_songs(self, xs, batch_size=32, sample_method="argmax", temperature=None, seed=None, uniforms=None, originals=None,
-                      note_events=False, close_at_end=False):
+                      note_events=False, close_at_end=False, judges=None, classes=None):
         """Decode whole songs and finish them on the device: ``xs`` is one decoder input list per song, as predict_indices takes them
         (``prepare_decoder_input`` with the song's own history); all songs run as ONE chip-filling decode.  Every engine batch's note,
         velocity and held buffers are copied on the device into window-major rolls of the whole run, and after the last batch
@@ -666,11 +676,17 @@ class Decoder(_ModelView):
         ``events``, its notes as an events.RECORD array sorted by (voice, start) (``close_at_end``: a note still sounding on the
         song's last row is closed there instead of dropped), and, where the model has the instrument head, ``programs``: the
         per-voice vote over the song's windows (events.vote_for_programs); the offsets and the records they count are two more
-        device-to-host reads.  Other arguments as predict_note_indices."""
+        device-to-host reads.  ``judges`` (style.Judges) with ``classes`` (one class per song): the three style classifiers read the
+        run's device rolls - the notes, the song-carried velocities after the rules, the instrument bytes, the way the reference's
+        autoencoded block sees a whole song (vae_evaluation.py:2248-2340) - and mvae_style_scores (midi_vae_amd.style) scores every
+        song against its class; every song's dict gains ``style``: judge -> accuracy and confidence, ``windows`` and the per-window
+        ``ensemble_prediction`` (n_i, C) float32 (None unless the model has the velocity and instrument heads and all three judges are
+        given); one more device-to-host read for the whole run.  Other arguments as predict_note_indices."""
         import torch
         from . import packers
         from . import reconstruction as rec
         from .rolls import as_rolls
+        from .style import style_of
         (s, p), sp = self._analysis(rec), self._s.spec
         packers.refuse_meta_without_instrument(s)
         if note_events:
@@ -685,6 +701,8 @@ class Decoder(_ModelView):
         for i, m in enumerate(lengths):
             if m <= 0:
                 raise ValueError("predict_songs: song %d has no windows - leave empty songs out of the list" % i)
+        if judges is not None and (classes is None or len(classes) != len(xs)):
+            raise ValueError("predict_songs: judges score every song against its class - pass one class per song")
         orig = None
         if originals is not None:
             originals = [np.asarray(as_rolls(o)) for o in originals]
@@ -706,6 +724,9 @@ class Decoder(_ModelView):
                 ev._check(sp.T, ep, n)
                 song = torch.from_numpy(ev.song_ordinals(lengths, n)).to(dev)
                 table = ev.run_on_device(rolls["notes"], outs[0], outs[1], song, len(lengths), ep, close_at_end)
+            if judges is not None:
+                tables = judges.probabilities(rolls["notes"], outs[0] if "velocity" in rolls else None, rolls.get("instr"), batch_size)
+                style_table, ensemble = judges.score_groups(tables, classes, lengths)
             velocity, starts, counts = (t.cpu().numpy() for t in outs)
             notes = rolls["notes"].cpu().numpy()
             instr = rolls["instr"].cpu().numpy() if "instr" in rolls else None
@@ -725,9 +746,121 @@ class Decoder(_ModelView):
                 d["events"] = song_events[i]
                 if programs is not None:
                     d["programs"] = programs[i]
+            if judges is not None:
+                d["style"] = dict(style_of(style_table[i]), ensemble_prediction=None if ensemble is None else ensemble[lo:lo + m])
             res.append(d)
             lo += m
         return res
+
+    def switch_styles(self, zs, classes, S=None, judges=None, note_events=False, batch_size=32, programs=None, close_at_end=False,
+                      sample_method="argmax", temperature=None, seed=None):
+        """The reference's ``switch_styles`` block (vae_evaluation.py:2448-2625) for songs that are already encoded: ``zs[i]`` (m_i, Z)
+        the latents of song i, ``classes[i]`` its class, ``S[i]`` (m_i, signature_vector_length) its signatures (None: zeros),
+        ``programs[i]`` the GM programs the original song plays (None: the instrument matrix and the ``SI_`` flag are not made).  For
+        every song and every OTHER class the coordinates ``C`` and ``C_switch`` of every window's z trade places and a window's
+        history is the previous switched z (style.switched_latents); all (song, target) pairs decode as ONE chip-filling pass
+        (``sample_method``, ``temperature``, ``seed`` as predict_note_indices).  The velocities follow the post-rules window by
+        window - the reference decodes every switched window in a call of its own (:2481-2483), no state is carried through a
+        song: mvae_sweep_windows' ``vel_out``, not the song-carried rule of predict_songs - and the signatures and harmonicity
+        come from mvae_desc_windows, all on the run's device rolls.  ``judges``
+        (style.Judges): the three style classifiers read those rolls on the device and mvae_style_scores runs twice on their
+        tables, against the ORIGINAL class (what the reference reports, :2500-2503) and against the target class.  Settings come
+        from ``decoder.sample_settings``.  dict: ``switch_instruments_matrix`` (:2608-2612, None without ``programs``) and ``pairs``,
+        one dict per (song, target) in the reference's order: ``song``, ``C``, ``C_switch``, ``notes`` (m, T) uint8, ``velocity``
+        (m, T) float32, ``signature`` (m, 15), ``harmonicity`` (m, max_voices, max_voices); with the instrument head ``instr``
+        (m, max_voices) uint8 and ``voted_programs`` (events.vote_for_programs); with ``programs`` ``instruments_switched`` (the
+        ``SI_`` of :2614-2619) and ``programs``, what the switched song is written with; with ``judges`` ``style`` (against C, with
+        the per-window ``ensemble_prediction``) and ``style_target`` (against C_switch); with ``note_events`` ``events`` for
+        midifile.write_midi (the held head's index where the model has one, else a note starts where the velocity after the rules
+        exceeds the threshold, as packers.process_decoder_indices derives D)."""
+        import torch
+        from . import descriptors, packers
+        from . import events as ev
+        from . import style as style_mod
+        from . import sweep as sweep_mod
+        (s, p), sp = self._analysis(sweep_mod), self._s.spec
+        _, dp = self._analysis(descriptors, True)
+        packers.refuse_meta_without_instrument(s)
+        if note_events:
+            _, ep = self._analysis(ev)
+        zs = [np.asarray(z, np.float64) for z in zs]
+        if len(classes) != len(zs) or (S is not None and len(S) != len(zs)) or (programs is not None and len(programs) != len(zs)):
+            raise ValueError("switch_styles: one class (and one signature array, one program list) per song")
+        for i, z in enumerate(zs):
+            if z.ndim != 2 or z.shape[0] <= 0 or z.shape[1] != sp.Z:
+                raise ValueError("switch_styles: the latents of song %d have shape %r, expected (m > 0, %d)" % (i, z.shape, sp.Z))
+            if not 0 <= int(classes[i]) < sp.C:
+                raise ValueError("switch_styles: song %d has class %r, the model has %d" % (i, classes[i], sp.C))
+        pairs = style_mod.switch_pairs(classes, sp.C)
+        if not pairs:
+            return dict(pairs=[], switch_instruments_matrix=None)
+        SD = int(packers._g(s, "signature_vector_length"))
+        xs = []
+        for song, C, C_switch in pairs:
+            switched, history = style_mod.switched_latents(zs[song], C, C_switch)
+            sig = np.zeros((switched.shape[0], SD)) if S is None else np.asarray(S[song])
+            xs.append(packers.prepare_decoder_input(s, switched, C_switch, sig, history))           # :2481
+        x = [np.concatenate([np.asarray(xi[k]) for xi in xs], 0) for k in range(len(xs[0]))]
+        lengths = [zs[song].shape[0] for song, _, _ in pairs]
+        n = int(sum(lengths))
+        rolls = self._sampled_run(x, batch_size, sinks.SongRolls(n), sample_method, temperature, seed, None)
+        notes_d, dev = rolls["notes"], rolls["notes"].device
+        V = sp.V
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            vel_d = None
+            if "velocity" in rolls:
+                vel_d = torch.empty((n, sp.T), dtype=torch.float32, device=dev)
+                sweep_mod.enqueue(notes_d.data_ptr(), rolls["velocity"].data_ptr(), notes_d.stride(1), notes_d.stride(0), n, sp.T, p, None,
+                                  vel_d, stream)
+            sig_d = torch.empty((n, descriptors.SIGNATURE_LENGTH), dtype=torch.float64, device=dev)
+            harm_d = torch.empty((n, V * V), dtype=torch.float64, device=dev)
+            descriptors.enqueue(notes_d.data_ptr(), notes_d.stride(1), notes_d.stride(0), n, sp.T, dp, sig_d, harm_d,
+                                descriptors._tonal_on(dev), stream)
+            if judges is not None:
+                tables = judges.probabilities(notes_d, vel_d, rolls.get("instr"), batch_size)
+                own = np.asarray([C for _, C, _ in pairs])
+                target = np.asarray([t for _, _, t in pairs])
+                style_table, ensemble = judges.score_groups(tables, own, lengths)
+                target_table, _ = judges.score_groups(tables, target, lengths)
+            if note_events:
+                ev._check(sp.T, ep, n)
+                song_of = torch.from_numpy(ev.song_ordinals(lengths, n)).to(dev)
+                if "held" in rolls:
+                    starts = rolls["held"]
+                elif vel_d is not None:
+                    starts = (~(vel_d.double() > p["threshold"])).to(torch.uint8)
+                else:
+                    starts = torch.ones((n, sp.T), dtype=torch.uint8, device=dev)
+                ev_table = ev.run_on_device(notes_d, vel_d, starts, song_of, len(lengths), ep, close_at_end)
+                song_events = ev.split_songs(*ev.read_back(ev_table[0], ev_table[1]), V)
+            notes = notes_d.cpu().numpy()
+            velocity = vel_d.cpu().numpy() if vel_d is not None else np.full((n, sp.T), p["default_velocity"], np.float32)
+            signature, harmonicity = sig_d.cpu().numpy(), harm_d.cpu().numpy().reshape(n, V, V)
+            instr = rolls["instr"].cpu().numpy() if "instr" in rolls else None
+        # (without the instrument head the reference decodes its default I, all piano, and votes on that)
+        voted = ev.vote_for_programs(instr, lengths, s) if instr is not None else [[0] * V for _ in pairs]
+        out, lo = [], 0
+        for k, ((song, C, C_switch), m) in enumerate(zip(pairs, lengths)):
+            d = dict(song=song, C=C, C_switch=C_switch, notes=notes[lo:lo + m], velocity=velocity[lo:lo + m],
+                     signature=signature[lo:lo + m], harmonicity=harmonicity[lo:lo + m])
+            if instr is not None:
+                d.update(instr=instr[lo:lo + m], voted_programs=voted[k])
+            if programs is not None:
+                original = [int(v) for v in programs[song]]
+                flag, used = style_mod.instruments_switched(original, voted[k], instr is not None)
+                d.update(instruments_switched=flag, programs=used)
+            if judges is not None:
+                d["style"] = dict(style_mod.style_of(style_table[k]), ensemble_prediction=None if ensemble is None else ensemble[lo:lo + m])
+                d["style_target"] = style_mod.style_of(target_table[k])
+            if note_events:
+                d["events"] = song_events[k]
+            out.append(d)
+            lo += m
+        matrix = None
+        if programs is not None:
+            matrix = style_mod.switch_instruments_matrix(pairs, [[int(v) for v in pr] for pr in programs], voted, sp.C)
+        return dict(pairs=out, switch_instruments_matrix=matrix)
 
     def predict_indices(self, x, batch_size=32, sample_method="argmax", temperature=None, seed=None, uniforms=None):
         """The decoded index of EVERY softmax head - dict 'notes' (n, T), 'instr' (n, max_voices), 'held' (n, T), 'next' (n, T)

@@ -220,14 +220,24 @@ def programs_of(instr, instrument_attach_method):
     raise NotImplementedError("instrument_attach_method %r: the sweep maps one-hot instrument heads only" % (instrument_attach_method,))
 
 
-def summarize(table, programs, counted=COUNTED):
+STYLE_KEYS = ("pitchstyle", "velocitystyle", "instrumentstyle")          # the columns of ``style``: one judge each
+
+
+def summarize(table, programs, counted=COUNTED, style=None):
     """the reference's summary dict ``name -> (strength, probability)`` of the K windows of one (sample, dimension) pair from their
     ``table`` (K, 22) and ``programs`` (K, V): the keys of evaluate_pitchroll, evaluate_velocityroll and evaluate_instrumentlist
-    (:1018-1114) without the three '*style' keys.  The pitch keys exist only if some window has a pitch, the velocity and
-    note-start keys only if some window has a note start; a window with an empty list is left out of the statistic lists and
-    counted (as 0) in the count lists."""
+    (:1018-1114); the three '*style' keys only with ``style`` (K, 3): the class-0 probability the pitch, velocity and instrument
+    style judges give every window (:1035-1039, :1089-1093, :1105-1109; a NaN column: that judge is absent).  The pitch keys exist
+    only if some window has a pitch, the velocity and note-start keys only if some window has a note start; a window with an empty
+    list is left out of the statistic lists and counted (as 0) in the count lists."""
     table = np.asarray(table, np.float64)
+    style = None if style is None else np.asarray(style, np.float64)
     d = {}
+
+    def judged(column):
+        if style is not None and not np.isnan(style[:, column]).all():
+            strength, probability, direction = strength_probability_direction(style[:, column].tolist())
+            d["mean_" + STYLE_KEYS[column] + "_" + direction] = (strength, probability)
 
     def statistic(name, stat, column, nonempty):
         strength, probability, direction = strength_probability_direction(table[nonempty, column].tolist())
@@ -244,14 +254,17 @@ def summarize(table, programs, counted=COUNTED):
         count("pitch", table[:, 0])
         count("specificpitch%d" % counted[0], table[:, 7])
         count("specificpitch%d" % counted[1], table[:, 8])
+        judged(0)
     has_start = table[:, 9] > 0
     if has_start.any():
+        judged(1)
         for i, stat in enumerate(_SIX):
             statistic("velocity", stat, 10 + i, has_start)
         for i, stat in enumerate(_SIX):
             statistic("note_starts", stat, 16 + i, has_start)
         count("note_starts", table[:, 9])
     programs = np.asarray(programs)
+    judged(2)
     steps = programs[1:] != programs[:-1]
     d["total_change_of_instruments"] = (float(steps.sum()) / float(steps.size) if steps.size else 0.0, 1.0)
     count("pianos", (programs == 0).sum(axis=1))
@@ -292,13 +305,14 @@ def _direction_rows(A):
     return steps.mean(axis=1), (A[:, 1:] >= A[:, :-1]).sum(axis=1) / (L - 1), descending
 
 
-def summarize_sweep(table, programs, counted=COUNTED):
-    """``table`` (n, Z, K, 22), ``programs`` (n, Z, K, V) -> (summaries[sample][dim], influence, most_peaked, overall_best):
-    ``summarize`` of every (sample, dimension) pair - taken for all pairs with lists of one length at once, a sweep has thousands
-    of pairs of a few numbers each - and ``influence`` of the result"""
+def summarize_sweep(table, programs, counted=COUNTED, style=None):
+    """``table`` (n, Z, K, 22), ``programs`` (n, Z, K, V), ``style`` (n, Z, K, 3) or None -> (summaries[sample][dim], influence,
+    most_peaked, overall_best): ``summarize`` of every (sample, dimension) pair - taken for all pairs with lists of one length at
+    once, a sweep has thousands of pairs of a few numbers each - and ``influence`` of the result"""
     table, programs = np.asarray(table, np.float64), np.asarray(programs)
     n, Z, K = table.shape[:3]
     t, pr = table.reshape(n * Z, K, N_COLUMNS), programs.reshape(n * Z, K, -1)
+    st = None if style is None else np.asarray(style, np.float64).reshape(n * Z, K, len(STYLE_KEYS))
     out = [dict() for _ in range(n * Z)]
 
     def put(rows, name, A):
@@ -312,9 +326,15 @@ def summarize_sweep(table, programs, counted=COUNTED):
         for r, pair, down in zip(rows.tolist(), zip(strength, probability), descending):
             out[r][name + ("_descending" if down else "_ascending")] = pair
 
-    def group(count_column, statistics, counts):
+    def judged(rows, column):
+        if st is not None and len(rows) and not np.isnan(st[:, :, column]).all():
+            put(rows, "mean_" + STYLE_KEYS[column], st[rows][:, :, column])
+
+    def group(count_column, statistics, counts, judge, judge_first):
         nonempty = t[:, :, count_column] > 0
         lengths = nonempty.sum(axis=1)
+        if judge_first:
+            judged(np.nonzero(lengths > 0)[0], judge)
         for L in np.unique(lengths[lengths > 0]):
             rows = np.nonzero(lengths == L)[0]
             sub, keep = t[rows], nonempty[rows]
@@ -324,13 +344,16 @@ def summarize_sweep(table, programs, counted=COUNTED):
         sub = t[rows]
         for name, column in counts:
             put(rows, "total_count_of_" + name, sub[:, :, column])
+        if not judge_first:
+            judged(rows, judge)
 
     with warnings.catch_warnings():
         warnings.simplefilter("ignore", RuntimeWarning)
         group(0, [(stat + "_pitch", 1 + i) for i, stat in enumerate(_SIX)],
-              [("pitch", 0), ("specificpitch%d" % counted[0], 7), ("specificpitch%d" % counted[1], 8)])
+              [("pitch", 0), ("specificpitch%d" % counted[0], 7), ("specificpitch%d" % counted[1], 8)], 0, False)
         group(9, [(stat + "_velocity", 10 + i) for i, stat in enumerate(_SIX)] + [(stat + "_note_starts", 16 + i) for i, stat in enumerate(_SIX)],
-              [("note_starts", 9)])
+              [("note_starts", 9)], 1, True)
+        judged(np.arange(n * Z), 2)
         steps = (pr[:, 1:] != pr[:, :-1]).reshape(n * Z, -1)
         for r in range(n * Z):
             out[r]["total_change_of_instruments"] = (float(steps[r].sum()) / float(steps.shape[1]) if steps.shape[1] else 0.0, 1.0)
