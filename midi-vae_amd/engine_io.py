@@ -101,6 +101,28 @@ class ArrayStaging(object):
             self._up_rows(name, np.zeros((B, width), np.float32) if val is None else np.asarray(val, np.float32), width)
             self._note_start(name, val)
 
+    def stage_decoder_paths(self, B, lo, paths):
+        """stage_decoder_inputs for the windows ``lo .. lo + B - 1`` of a generated run (``paths``: generation.upload's device copy of
+        the anchors and the recipe, made once per run): mvae_latent_paths writes zh[:B, :Z] and the history zh[:B, Z:2Z] in place,
+        nothing crosses from the host.  Padding rows, the additional columns and the start inputs are zero - the reference generates
+        with C = 0 and S = 0 (vae_evaluation.py:726-728, :854-861)."""
+        from . import generation
+        s = self.spec
+        if int(paths["anchors"].shape[1]) != s.Z or not paths["anchors"].is_cuda:
+            raise ValueError("the run's anchors are (m, %d) on the engine's device" % s.Z)
+        Bp = self.pad16(B)
+        zh = self._v("zh", Bp, s.zin)
+        zh[B:].zero_()
+        generation.enqueue(paths, lo, B, zh[:B, :s.Z], zh[:B, s.Z:2 * s.Z] if s.history else None,
+                           torch.cuda.current_stream(self.device).cuda_stream)
+        if s.add_dim:
+            zh[:, s.zin - s.add_dim:].zero_()
+        for name, width in (("in.start_notes", s.Dout), ("in.start_instr", s.ID), ("in.start_vel", 1), ("in.start_held", 2),
+                            ("in.start_next", s.Dout)):
+            if name in self.store:
+                self.store[name][:Bp * width].zero_()
+                self._note_start(name, None)
+
     def stage_targets(self, B, y_idx, c_idx=None, w_notes=None, w_instr=None, w_vel=None, w_style=None, n_idx=None,
                       w_held=None, w_next=None, sig=None, w_sig=None, w_cnotes=None, w_cinstr=None, ya_idx=None):
         """Targets and Keras sample weights.  Row weights are folded with the weighted-objective normalisers

@@ -219,6 +219,29 @@ STYLE_SIGNATURES = {
     "mvae_style_scores": (_i32, [C.POINTER(StyleArgs), _vp]),
 }
 
+
+class PathsArgs(C.Structure):
+    """mvae_paths_args of include/midivae_generate.h"""
+    _fields_ = [("anchors", _vp), ("a0", _vp), ("a1", _vp), ("c0", _vp), ("c1", _vp), ("first_window", _vp), ("n", _i32), ("lo", _i32),
+                ("count", _i32), ("Z", _i32), ("n_anchors", _i32), ("ld_anchor", _i32), ("anchor_f64", _i32), ("ld_z", _i32),
+                ("ld_hist", _i32), ("reserved", _i32), ("z_out", _vp), ("hist_out", _vp)]
+
+
+class PianorollArgs(C.Structure):
+    """mvae_pianoroll_args of include/midivae_generate.h"""
+    _fields_ = [("idx", _vp), ("stride_t", _i64), ("stride_w", _i64), ("vel", _vp), ("first_window", _vp), ("n", _i32), ("T", _i32),
+                ("voices", _i32), ("silent", _i32), ("n_pitch", _i32), ("ld_img", _i32), ("threshold", C.c_double),
+                ("max_velocity", C.c_double), ("img_out", _vp)]
+
+
+GENERATE_ABI_VERSION = 1
+# the eighth header, include/midivae_generate.h (versioned on its own, like the second to seventh)
+GENERATE_SIGNATURES = {
+    "mvae_generate_abi_version": (_i32, []),
+    "mvae_latent_paths": (_i32, [C.POINTER(PathsArgs), _vp]),
+    "mvae_pianoroll": (_i32, [C.POINTER(PianorollArgs), _vp]),
+}
+
 # name -> (restype, argtypes); every symbol include/midivae_hip.h declares
 SIGNATURES = {
     "mvae_abi_version": (_i32, []),
@@ -295,6 +318,8 @@ HEADERS = (("", "mvae_abi_version", ABI_VERSION, SIGNATURES),
            ("note events ", "mvae_events_abi_version", EVENTS_ABI_VERSION, EVENTS_SIGNATURES),
            ("import ", "mvae_import_abi_version", IMPORT_ABI_VERSION, IMPORT_SIGNATURES),
            ("style ", "mvae_style_abi_version", STYLE_ABI_VERSION, STYLE_SIGNATURES))
+# the headers after the seventh, checked by load() right behind HEADERS in the same way
+LATER_HEADERS = (("generate ", "mvae_generate_abi_version", GENERATE_ABI_VERSION, GENERATE_SIGNATURES),)
 
 _lib = None
 
@@ -313,7 +338,7 @@ def load():
             "%s not found - build it with `make -C midi-vae_amd/csrc` (or __graft_entry__.build()); "
             "the MIDI-VAE engine has no CPU fallback" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for what, version, want, signatures in HEADERS:
+    for what, version, want, signatures in HEADERS + LATER_HEADERS:
         for name, (res, args) in signatures.items():
             fn = getattr(lib, name)      # AttributeError here = ABI drift between header and library
             fn.restype = res

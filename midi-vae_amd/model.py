@@ -480,21 +480,28 @@ class Decoder(_ModelView):
                 i += 1
         return res
 
-    def _run(self, x, batch_size, sink, sample=None):
+    def _run(self, x, batch_size, sink, sample=None, stage=None):
         """decoder forward over all windows at the forward-only engine's batch (``batch_size`` is the caller's: results are per
         window); every rank decodes everything it is given - decoding is pure replicas.  ``sink`` (decode_sinks)
         says what the decode keeps, takes every engine batch's device buffers behind the decode and makes the result.  ``sample``:
         the resolved arguments of a 'choice' decode (_sample_spec) - every engine batch is told the caller's index of its first
         window, so a window's draws do not depend on the batches.  Engine.decode keys its recorded step plans on the VALUES it is
-        given: without a sample and a velocity request this is the plain ``eng.decode(B, want_probs=...)`` and replays that plan."""
-        a = self._unpack(x)
-        z = np.asarray(a.pop("z"))
-        n = z.shape[0]
+        given: without a sample and a velocity request this is the plain ``eng.decode(B, want_probs=...)`` and replays that plan.
+        ``stage``: instead of ``x``, a pair (n, fn) - ``fn(eng, lo, hi)`` stages the decoder inputs of the windows lo .. hi - 1 of a
+        run of n itself (decode_paths: on the device, from the run's anchors)."""
+        if stage is None:
+            a = self._unpack(x)
+            z = np.asarray(a.pop("z"))
+            n = z.shape[0]
+            fill = lambda eng, lo, hi: eng.stage_decoder_inputs(hi - lo, z=z[lo:hi], **{k: (None if v is None else np.asarray(v)[lo:hi])
+                                                                                        for k, v in a.items()})
+        else:
+            n, fill = stage
         eng = self._s.get_infer(n)
         for lo in range(0, n, eng.maxB):
             hi = min(n, lo + eng.maxB)
             B = hi - lo
-            eng.stage_decoder_inputs(B, z=z[lo:hi], **{k: (None if v is None else np.asarray(v)[lo:hi]) for k, v in a.items()})
+            fill(eng, lo, hi)
             spec = None
             if sample is not None:
                 spec = dict(sample, first_window=lo, uniforms={k: u[lo:hi] for k, u in (sample.get("uniforms") or {}).items()})
@@ -657,7 +664,7 @@ class Decoder(_ModelView):
         return res
 
     def predict_songs(self, xs, batch_size=32, sample_method="argmax", temperature=None, seed=None, uniforms=None, originals=None,
-                      note_events=False, close_at_end=False, judges=None, classes=None):
+                      note_events=False, close_at_end=False, judges=None, classes=None, pianoroll=False):
         """Decode whole songs and finish them on the device: ``xs`` is one decoder input list per song, as predict_indices takes them
         (``prepare_decoder_input`` with the song's own history); all songs run as ONE chip-filling decode.  Every engine batch's note,
         velocity and held buffers are copied on the device into window-major rolls of the whole run, and after the last batch
@@ -681,17 +688,15 @@ class Decoder(_ModelView):
         autoencoded block sees a whole song (vae_evaluation.py:2248-2340) - and mvae_style_scores (midi_vae_amd.style) scores every
         song against its class; every song's dict gains ``style``: judge -> accuracy and confidence, ``windows`` and the per-window
         ``ensemble_prediction`` (n_i, C) float32 (None unless the model has the velocity and instrument heads and all three judges are
-        given); one more device-to-host read for the whole run.  Other arguments as predict_note_indices."""
-        import torch
+        given); one more device-to-host read for the whole run.  ``pianoroll``: mvae_pianoroll (midi_vae_amd.pianoroll) draws the
+        run's device rolls with the velocities after the rules and every song's dict gains ``pianoroll`` (n_pitch, ticks) float64,
+        the reference's prepare_for_drawing(Y, V) of the song; one more read.  Other arguments as predict_note_indices."""
         from . import packers
         from . import reconstruction as rec
         from .rolls import as_rolls
-        from .style import style_of
         (s, p), sp = self._analysis(rec), self._s.spec
         packers.refuse_meta_without_instrument(s)
-        if note_events:
-            from . import events as ev
-            _, ep = self._analysis(ev)
+        self._check_song_extras(note_events, pianoroll)
         xs = [_as_list(x) for x in xs]
         if not xs:
             return []
@@ -715,6 +720,31 @@ class Decoder(_ModelView):
         x = [np.concatenate([np.asarray(xi[k]) for xi in xs], 0) for k in range(len(xs[0]))]
         n = int(sum(lengths))
         rolls = self._sampled_run(x, batch_size, sinks.SongRolls(n), sample_method, temperature, seed, uniforms)
+        return self._finish_songs(rolls, lengths, orig, note_events, close_at_end, judges, classes, batch_size, pianoroll)
+
+    def _check_song_extras(self, note_events, pianoroll):
+        """the refusals of what predict_songs and decode_paths run behind the decode, before anything is decoded"""
+        if note_events:
+            from . import events as ev
+            self._analysis(ev)
+        if pianoroll:
+            from . import pianoroll as pr
+            self._analysis(pr)
+
+    def _finish_songs(self, rolls, lengths, orig, note_events, close_at_end, judges, classes, batch_size, pianoroll):
+        """what follows the decode of whole songs, on the run's device rolls (SongRolls): mvae_recon_songs, then as asked
+        mvae_note_events, the style judges and mvae_pianoroll; one dict per song (predict_songs describes it)"""
+        import torch
+        from . import reconstruction as rec
+        from .style import style_of
+        (s, p), sp = self._analysis(rec), self._s.spec
+        if note_events:
+            from . import events as ev
+            _, ep = self._analysis(ev)
+        if pianoroll:
+            from . import pianoroll as pr
+            _, pp = self._analysis(pr)
+        n = int(sum(lengths))
         dev = rolls["notes"].device
         with torch.cuda.device(dev):
             first = torch.from_numpy(rec.first_windows(lengths, n)).to(dev)
@@ -727,6 +757,8 @@ class Decoder(_ModelView):
             if judges is not None:
                 tables = judges.probabilities(rolls["notes"], outs[0] if "velocity" in rolls else None, rolls.get("instr"), batch_size)
                 style_table, ensemble = judges.score_groups(tables, classes, lengths)
+            if pianoroll:
+                images = pr.split_songs(pr.run_on_device(rolls["notes"], outs[0], first, pp).cpu().numpy(), lengths, sp.T // sp.V)
             velocity, starts, counts = (t.cpu().numpy() for t in outs)
             notes = rolls["notes"].cpu().numpy()
             instr = rolls["instr"].cpu().numpy() if "instr" in rolls else None
@@ -748,9 +780,68 @@ class Decoder(_ModelView):
                     d["programs"] = programs[i]
             if judges is not None:
                 d["style"] = dict(style_of(style_table[i]), ensemble_prediction=None if ensemble is None else ensemble[lo:lo + m])
+            if pianoroll:
+                d["pianoroll"] = images[i]
             res.append(d)
             lo += m
         return res
+
+    def decode_paths(self, paths, batch_size=32, sample_method="argmax", temperature=None, seed=None, note_events=False,
+                     close_at_end=False, pianoroll=False):
+        """Decode generated songs - interpolation songs and medleys (reference vae_evaluation.py:705-887) - and finish them on the
+        device.  ``paths``: one path per song (midi_vae_amd.generation: ``interpolation_path``, ``medley_path``), all with host
+        anchors or all with device tensors of one type.  Anchors and recipe are uploaded once; every engine batch's z and history
+        rows are written in place by mvae_latent_paths (Engine.stage_decoder_paths) with C = 0, a zero signature and zero start
+        inputs, as the reference generates; all songs are ONE chip-filling decode, and what follows is predict_songs' own tail:
+        mvae_recon_songs, with ``note_events`` mvae_note_events, with ``pianoroll`` mvae_pianoroll.  One dict per song as
+        predict_songs returns it, plus ``z`` (m_i, Z) float32, the latent rows the decoder read (one more call of the kernel into a
+        tensor of the whole run).  Other arguments as predict_songs."""
+        import torch
+        from . import generation as gen
+        from . import packers
+        from . import reconstruction as rec
+        (s, _), sp = self._analysis(rec), self._s.spec
+        packers.refuse_meta_without_instrument(s)
+        self._check_song_extras(note_events, pianoroll)
+        paths = list(paths)
+        if not paths:
+            return []
+        run = gen.concat_paths(paths)
+        if int(run["anchors"].shape[1]) != sp.Z:
+            raise ValueError("decode_paths: the anchors have %d columns, the model's latent has %d" % (run["anchors"].shape[1], sp.Z))
+        lengths, n = run["lengths"], len(run["a0"])
+        sample = self._sample_spec(n, sample_method, temperature, seed, None, self._softmax_heads())
+        state = {}
+
+        def fill(eng, lo, hi):
+            if "run" not in state:          # (once per run: the engine, and with it the device, exists from here on)
+                state["run"] = gen.upload(run, eng.device)
+            eng.stage_decoder_paths(hi - lo, lo, state["run"])
+
+        rolls = self._run(None, batch_size, sinks.SongRolls(n), sample, stage=(n, fill))
+        dev = rolls["notes"].device
+        with torch.cuda.device(dev):
+            z_dev = torch.empty((n, sp.Z), dtype=torch.float32, device=dev)
+            gen.enqueue(state["run"], 0, n, z_dev, None, torch.cuda.current_stream().cuda_stream)
+            z = z_dev.cpu().numpy()
+        res = self._finish_songs(rolls, lengths, None, note_events, close_at_end, None, None, batch_size, pianoroll)
+        lo = 0
+        for d, m in zip(res, lengths):
+            d["z"] = z[lo:lo + m]
+            lo += m
+        return res
+
+    def interpolation_songs(self, code_pairs, length, mode="lerp", **kw):
+        """the reference's random interpolation songs (:841-887): for every pair of codes one song of ``length + 1`` windows;
+        ``kw`` as decode_paths"""
+        from . import generation as gen
+        return self.decode_paths([gen.interpolation_path(a, b, length, mode) for a, b in code_pairs], **kw)
+
+    def medleys(self, list_of_Rs, interpolation_length, mode="lerp", **kw):
+        """the reference's medleys (:705-837): for every list of encoded songs ``Rs`` one song - their windows, bridged through
+        latent space by ``interpolation_length`` windows; ``kw`` as decode_paths"""
+        from . import generation as gen
+        return self.decode_paths([gen.medley_path(Rs, interpolation_length, mode) for Rs in list_of_Rs], **kw)
 
     def switch_styles(self, zs, classes, S=None, judges=None, note_events=False, batch_size=32, programs=None, close_at_end=False,
                       sample_method="argmax", temperature=None, seed=None):
