@@ -18,7 +18,12 @@ first, so the songs only show the pipeline working - not the paper's results: af
 argmax of most rows is the silent column and the files are nearly empty; ``--sample-method choice`` draws notes.
 
     python generate_songs.py [--epochs 3] [--songs 8] [--medleys 2] [--interpolations 2] [--sample-method argmax|choice]
-                             [--midi-dir DIR] [--out-dir generated]
+                             [--random N] [--long N [--long-length 20]] [--midi-dir DIR] [--out-dir generated]
+
+``--random N`` adds the reference's random songs (:1771-1814): N one-window songs from random codes (``random_<i>.mid``) and, per code,
+one window per class with the class knob turned (``random_<i>_<C>.mid``).  ``--long N`` adds its long songs (:1821-1896): N songs of
+``--long-length`` windows that walk from a random code through the training codes, every window decoded, fed back and encoded on the
+device (decoder.long_songs); ``random_long_<i>.mid`` with the programs voted over the song's windows.
 """
 import argparse
 import os
@@ -50,6 +55,9 @@ def main():
     ap.add_argument("--mode", choices=("lerp", "slerp"), default="lerp")
     ap.add_argument("--sample-method", choices=("argmax", "choice"), default="argmax",
                     help="'argmax' is what the reference generates with (:709, :845); 'choice' draws from the tempered softmax on the device")
+    ap.add_argument("--random", type=int, default=0, help="max_new_sampled_songs")
+    ap.add_argument("--long", type=int, default=0, help="max_new_sampled_long_songs")
+    ap.add_argument("--long-length", type=int, default=20, help="long_song_length")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--midi-dir", default=None, help="read the songs from this folder (one subfolder per class) instead of making them")
     ap.add_argument("--out-dir", default="generated")
@@ -107,10 +115,25 @@ def main():
         paths.append(generation.interpolation_path(as_type(random_code_1), as_type(random_code_2), args.length, args.mode))
         names.append("random_interpolation_%d_length_%d" % (i, args.length))
         infos.append(None)
-    if not paths:
+    if not paths and not args.random and not args.long:
         raise SystemExit("nothing to generate")
     kw = dict(seed=args.seed) if args.sample_method == "choice" else {}
-    res = model.decoder.decode_paths(paths, batch_size=bs, sample_method=args.sample_method, note_events=True, pianoroll=True, **kw)
+    decode = dict(batch_size=bs, sample_method=args.sample_method, note_events=True, pianoroll=True, **kw)
+    res = model.decoder.decode_paths(paths, **decode) if paths else []
+    if args.random:                                                                                             # :1771-1814
+        codes = rng.normal(loc=0.0, scale=z_std_train, size=(args.random, s["latent_dim"]))
+        res += model.decoder.random_songs(codes, **decode)
+        names += ["random_%d" % i for i in range(args.random)]
+        for i in range(args.random):
+            random_code = rng.normal(loc=0.0, scale=z_std_train, size=(s["latent_dim"],))
+            res += model.decoder.class_knob_songs(random_code, s["num_classes"], **decode)
+            names += ["random_%d_%d" % (i, C) for C in range(s["num_classes"])]
+        infos += [None] * (args.random * (1 + s["num_classes"]))
+    if args.long:                                                                                               # :1821-1896
+        codes = rng.normal(loc=0.0, scale=z_std_train, size=(args.long, s["latent_dim"]))
+        res += model.decoder.long_songs(all_z, codes, length=args.long_length, **decode)
+        names += ["random_long_%d" % i for i in range(args.long)]
+        infos += [None] * args.long
     dt = time.time() - t0
 
     os.makedirs(args.out_dir, exist_ok=True)
@@ -125,7 +148,7 @@ def main():
         print("%-60s %4d windows %5d notes, image %s, programs %s" % (name, len(d["notes"]), len(d["events"]), d["pianoroll"].shape,
                                                                       list(d.get("programs", []))))
     n_win = sum(len(d["notes"]) for d in res)
-    print("%d windows of %d songs: encode, one decode pass, rules, note events and images on the device: %.2f s; files in %s"
+    print("%d windows of %d songs: encode, decode passes, rules, note events and images on the device: %.2f s; files in %s"
           % (n_win, len(res), dt, args.out_dir))
 
 

@@ -138,3 +138,21 @@ class SongRolls(Sink):
 
     def result(self):
         return self.rolls
+
+
+class LockstepRolls(SongRolls):
+    """long_songs: S songs of ``length`` windows decode in lockstep, one window of every song per engine batch; the rolls of the run
+    stay song-contiguous - window ``it`` of song ``s`` is row ``s * length + it`` - so a batch's columns go to every length-th row"""
+
+    def __init__(self, songs, length):
+        SongRolls.__init__(self, songs * length)
+        self.length = length
+
+    def batch_at(self, eng, it, first_song, count, views):
+        import torch
+        rows = slice(first_song * self.length + it, (first_song + count) * self.length, self.length)
+        for k in ("notes", "velocity", "held", "instr"):
+            if k in views:
+                if k not in self.rolls:
+                    self.rolls[k] = torch.empty((self.n, views[k].shape[0]), dtype=views[k].dtype, device=eng.device)
+                self.rolls[k][rows].copy_(views[k][:, :count].t())

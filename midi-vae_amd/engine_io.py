@@ -123,6 +123,64 @@ class ArrayStaging(object):
                 self.store[name][:Bp * width].zero_()
                 self._note_start(name, None)
 
+    def _zero_decoder_extras(self, Bp):
+        """the additional columns and the start inputs of a generated batch: C = 0, S = 0, zero start rows"""
+        s = self.spec
+        if s.add_dim:
+            self._v("zh", Bp, s.zin)[:, s.zin - s.add_dim:].zero_()
+        for name, width in (("in.start_notes", s.Dout), ("in.start_instr", s.ID), ("in.start_vel", 1), ("in.start_held", 2),
+                            ("in.start_next", s.Dout)):
+            if name in self.store:
+                self.store[name][:Bp * width].zero_()
+                self._note_start(name, None)
+
+    def stage_decoder_walk(self, B, walk_state):
+        """stage_decoder_inputs for one iteration of ``B`` long songs in lockstep (reference vae_evaluation.py:1844-1866):
+        mvae_nearest_walk searches ``walk_state['all_z']`` for every song's nearest code not picked before, appends it to
+        ``picked`` and writes the pulled code into zh[:B, :Z] and the code pulled one iteration earlier (``hist_in``; None: zeros) into the
+        history zh[:B, Z:2Z], in place.  ``r_in`` None: the songs' codes are what Engine.encode left in zh[:B, :Z] - the kernel reads an
+        element before it writes it.  Other keys as longsongs.enqueue_walk takes them: n_picked, e, den, workspace, best_out,
+        dist_out, r_out.  Padding rows, the additional columns and the start inputs are zero (C = 0, S = 0, :1831, :1840)."""
+        from . import longsongs
+        s = self.spec
+        w = walk_state
+        if int(w["all_z"].shape[1]) != s.Z or not w["all_z"].is_cuda:
+            raise ValueError("all_z is (N, %d) on the engine's device" % s.Z)
+        Bp = self.pad16(B)
+        zh = self._v("zh", Bp, s.zin)
+        z = zh[:B, :s.Z]
+        longsongs.enqueue_walk(w["all_z"], z if w.get("r_in") is None else w["r_in"], w.get("hist_in"), w["picked"], w["n_picked"], w["e"],
+                               w["den"], w["workspace"], w["best_out"], w["dist_out"], z, w["r_out"],
+                               zh[:B, s.Z:2 * s.Z] if s.history else None, torch.cuda.current_stream(self.device).cuda_stream)
+        zh[B:].zero_()
+        self._zero_decoder_extras(Bp)
+
+    def stage_encoder_feedback(self, B, decoded_views, eps_dev, p):
+        """stage_encoder_inputs from what the last decode of ``B`` windows left on the device (``decoded_views``: Engine.decoded):
+        mvae_feedback_rows turns the note, velocity, held and instrument buffers into in.x_idx, in.x_idx_rev, in.vel, in.d_idx and
+        in.i_idx - process_decoder_outputs of one window a call followed by prepare_encoder_input_list (reference
+        vae_evaluation.py:1870-1887), padding columns zero as the host staging leaves them.  ``eps_dev`` (B, Z) float32 on the device:
+        the encode's epsilon rows, already scaled.  ``p``: longsongs.params(settings)."""
+        from . import longsongs
+        s = self.spec
+        if s.attach:
+            raise NotImplementedError("attach_instruments: the decoded rows do not carry the attached instrument column")
+        Bp = self.pad16(B)
+        self.norm_B = float(B)
+        notes = decoded_views["notes"]
+        if p["voices"] != s.V or tuple(notes.shape) != (s.T, Bp):
+            raise ValueError("the decoded views are those of a decode of %d windows of this engine" % B)
+        tm = lambda t: None if t is None else t[:, :B].t()          # (n, T) views of the time-major buffers
+        eps = self._v("in.eps", Bp, s.Z)
+        eps[:B].copy_(eps_dev)
+        eps[B:].zero_()
+        longsongs.enqueue_feedback(
+            tm(notes), tm(decoded_views.get("velocity")), tm(decoded_views.get("held")), tm(decoded_views.get("instr")), p, Bp,
+            self._v("in.x_idx", s.T, Bp), self._v("in.x_idx_rev", s.T, Bp) if self.enc_bi else None,
+            self._v("in.vel", s.T, Bp) if s.meta_velocity else None, self._v("in.d_idx", s.T, Bp) if s.meta_held else None,
+            self._v("in.i_idx", s.V, Bp) if s.meta_instrument else None, torch.cuda.current_stream(self.device).cuda_stream)
+        return B
+
     def stage_targets(self, B, y_idx, c_idx=None, w_notes=None, w_instr=None, w_vel=None, w_style=None, n_idx=None,
                       w_held=None, w_next=None, sig=None, w_sig=None, w_cnotes=None, w_cinstr=None, ya_idx=None):
         """Targets and Keras sample weights.  Row weights are folded with the weighted-objective normalisers

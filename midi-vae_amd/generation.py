@@ -77,6 +77,11 @@ def interpolation_path(code_a, code_b, length, mode="lerp"):
     return dict(_table(rows), anchors=np.stack([a, b]))
 
 
+def code_path(code):
+    """a song of ONE window that is the code itself ((Z,) or (1, Z); reference vae_evaluation.py:1776-1779): a copy row, no blend"""
+    return dict(_table([(0, -1, 1.0, 0.0)]), anchors=_host_code(code).reshape(1, -1))
+
+
 def medley_path(Rs, interpolation_length, mode="lerp"):
     """a medley (:731-822): the rows of ``Rs[0]``, then for every later song ``interpolation_length`` bridge windows from the previous
     song's LAST row to this song's FIRST row at t = i / float(interpolation_length), i = 0.., then its own rows.  ``Rs``: (m_i, Z)

@@ -242,6 +242,31 @@ GENERATE_SIGNATURES = {
     "mvae_pianoroll": (_i32, [C.POINTER(PianorollArgs), _vp]),
 }
 
+class WalkArgs(C.Structure):
+    """mvae_walk_args of include/midivae_longsong.h"""
+    _fields_ = [("all_z", _vp), ("r_in", _vp), ("hist_in", _vp), ("picked", _vp), ("workspace", _vp), ("N", _i32), ("S", _i32), ("Z", _i32),
+                ("ld_all", _i32), ("ld_r", _i32), ("r_f64", _i32), ("ld_hist_in", _i32), ("hist_f64", _i32), ("cap", _i32),
+                ("n_picked", _i32), ("ld_z", _i32), ("ld_rout", _i32), ("ld_hist", _i32), ("reserved", _i32), ("e", C.c_double),
+                ("den", C.c_double), ("best_out", _vp), ("dist_out", _vp), ("z_out", _vp), ("r_out", _vp), ("hist_out", _vp)]
+
+
+class FeedbackArgs(C.Structure):
+    """mvae_feedback_args of include/midivae_longsong.h"""
+    _fields_ = [("idx", _vp), ("stride_t", _i64), ("stride_w", _i64), ("vel", _vp), ("held_idx", _vp), ("instr", _vp),
+                ("instr_stride_v", _i64), ("instr_stride_w", _i64), ("n", _i32), ("T", _i32), ("voices", _i32), ("silent", _i32),
+                ("n_pitch", _i32), ("override_rules", _i32), ("threshold", C.c_double), ("ld_out", _i32), ("reserved", _i32),
+                ("x_out", _vp), ("x_rev_out", _vp), ("vel_out", _vp), ("held_out", _vp), ("instr_out", _vp)]
+
+
+LONGSONG_ABI_VERSION = 1
+# the ninth header, include/midivae_longsong.h (versioned on its own, like the second to eighth)
+LONGSONG_SIGNATURES = {
+    "mvae_longsong_abi_version": (_i32, []),
+    "mvae_nearest_walk_workspace": (_sz, [_i32, _i32, _i32]),
+    "mvae_nearest_walk": (_i32, [C.POINTER(WalkArgs), _vp]),
+    "mvae_feedback_rows": (_i32, [C.POINTER(FeedbackArgs), _vp]),
+}
+
 # name -> (restype, argtypes); every symbol include/midivae_hip.h declares
 SIGNATURES = {
     "mvae_abi_version": (_i32, []),
@@ -320,6 +345,8 @@ HEADERS = (("", "mvae_abi_version", ABI_VERSION, SIGNATURES),
            ("style ", "mvae_style_abi_version", STYLE_ABI_VERSION, STYLE_SIGNATURES))
 # the headers after the seventh, checked by load() right behind HEADERS in the same way
 LATER_HEADERS = (("generate ", "mvae_generate_abi_version", GENERATE_ABI_VERSION, GENERATE_SIGNATURES),)
+# ... and the ninth (a tuple of its own: LATER_HEADERS stays what the eighth header's tests pin)
+LONGSONG_HEADERS = (("long song ", "mvae_longsong_abi_version", LONGSONG_ABI_VERSION, LONGSONG_SIGNATURES),)
 
 _lib = None
 
@@ -338,7 +365,7 @@ def load():
             "%s not found - build it with `make -C midi-vae_amd/csrc` (or __graft_entry__.build()); "
             "the MIDI-VAE engine has no CPU fallback" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for what, version, want, signatures in HEADERS + LATER_HEADERS:
+    for what, version, want, signatures in HEADERS + LATER_HEADERS + LONGSONG_HEADERS:
         for name, (res, args) in signatures.items():
             fn = getattr(lib, name)      # AttributeError here = ABI drift between header and library
             fn.restype = res

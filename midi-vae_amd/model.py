@@ -731,9 +731,10 @@ class Decoder(_ModelView):
             from . import pianoroll as pr
             self._analysis(pr)
 
-    def _finish_songs(self, rolls, lengths, orig, note_events, close_at_end, judges, classes, batch_size, pianoroll):
+    def _finish_songs(self, rolls, lengths, orig, note_events, close_at_end, judges, classes, batch_size, pianoroll, carried=True):
         """what follows the decode of whole songs, on the run's device rolls (SongRolls): mvae_recon_songs, then as asked
-        mvae_note_events, the style judges and mvae_pianoroll; one dict per song (predict_songs describes it)"""
+        mvae_note_events, the style judges and mvae_pianoroll; one dict per song (predict_songs describes it).  ``carried`` False: the
+        velocity rules start afresh in every window (long_songs: the reference post-processes one window a call there)"""
         import torch
         from . import reconstruction as rec
         from .style import style_of
@@ -749,7 +750,7 @@ class Decoder(_ModelView):
         with torch.cuda.device(dev):
             first = torch.from_numpy(rec.first_windows(lengths, n)).to(dev)
             outs = rec.run_on_device(rolls["notes"], rolls.get("velocity"), rolls.get("held"), None if orig is None else torch.from_numpy(orig).to(dev),
-                                     first, p)
+                                     first if carried else None, p)
             if note_events:
                 ev._check(sp.T, ep, n)
                 song = torch.from_numpy(ev.song_ordinals(lengths, n)).to(dev)
@@ -842,6 +843,126 @@ class Decoder(_ModelView):
         latent space by ``interpolation_length`` windows; ``kw`` as decode_paths"""
         from . import generation as gen
         return self.decode_paths([gen.medley_path(Rs, interpolation_length, mode) for Rs in list_of_Rs], **kw)
+
+    def random_songs(self, codes, **kw):
+        """the reference's random songs (vae_evaluation.py:1771-1785): every row of ``codes`` (n, Z) - drawn by the caller as the
+        reference draws them, np.random.normal(0, z_std_train) - is a song of ONE window with C = 0, S = 0 and a zero history; all of
+        them are one decode_paths run.  ``kw`` and the song dicts as decode_paths"""
+        from . import generation as gen
+        codes = np.asarray(codes)
+        if codes.ndim != 2 or codes.shape[0] <= 0:
+            raise ValueError("random_songs: codes are (n > 0, Z), got %r" % (codes.shape,))
+        return self.decode_paths([gen.code_path(c) for c in codes], **kw)
+
+    @staticmethod
+    def class_knob_codes(code, num_classes):
+        """(num_classes, Z): row C is ``code`` with the columns 0 .. num_classes-1 set to -1 and column C to 1 (:1793-1797)"""
+        code = np.asarray(code).reshape(-1)
+        if code.dtype not in (np.float32, np.float64):
+            code = code.astype(np.float64)
+        num_classes = int(num_classes)
+        if not 1 <= num_classes <= code.shape[0]:
+            raise ValueError("class_knob_songs: %d classes for a code of %d columns" % (num_classes, code.shape[0]))
+        out = np.repeat(code[None, :], num_classes, 0)
+        out[:, :num_classes] = -1
+        out[np.arange(num_classes), np.arange(num_classes)] = 1
+        return out
+
+    def class_knob_songs(self, code, num_classes, **kw):
+        """the reference's class knob (:1787-1814): one random ``code`` (Z,), decoded once per class with the first ``num_classes``
+        latent columns turned to that class (class_knob_codes) - ``num_classes`` songs of one window each, in class order, as
+        random_songs returns them.  With ``pianoroll=True`` the caller forms pianoroll.difference_image of neighbouring classes
+        (the reference's _switchdiff pictures)"""
+        return self.random_songs(self.class_knob_codes(code, num_classes), **kw)
+
+    def long_songs(self, all_z, codes, length=20, e=None, sample_method="argmax", temperature=None, seed=None, note_events=False,
+                   pianoroll=False, close_at_end=False, batch_size=32):
+        """The reference's long-song generator (vae_evaluation.py:1821-1896) for S songs in lockstep, without the host between two
+        passes.  ``all_z`` (N, Z) float32 the training codes, ``codes`` (S, Z) float64 or float32 the random start codes, drawn by
+        the caller as the reference draws them; ``e`` the pull's weight (None: np.std(all_z), the reference's z_std_train).  Every
+        one of the ``length`` iterations is, per group of songs the forward-only engine takes at once: mvae_nearest_walk
+        (Engine.stage_decoder_walk: the nearest code not picked before, the pull, z and history written in place), one decode,
+        mvae_feedback_rows (Engine.stage_encoder_feedback: the decoded batch as encoder input) and one encode, whose z the next
+        search reads where the encoder left it.  all_z and codes are uploaded once; the epsilons of all ``length`` encodes are taken
+        from the model's stream up front (iteration-major, one row per song; zeros at epsilon_std = 0) and uploaded once; the encode
+        behind the last decode, whose code nobody reads, is not run.  A 'choice' decode keys window (iteration it, song s) as window
+        it * S + s of the run: a song's draws depend on S.  Every iteration's decode buffers go into song-contiguous rolls of the
+        run and predict_songs' tail runs once on them, with the velocity rules restarted in every window as the reference applies
+        them here.  One dict per song as predict_songs returns it (``programs``: events.vote_for_programs over the song's windows,
+        :1890, with or without ``note_events``), plus ``picked`` (length,) the indices of the codes walked to, ``distances``
+        (length,) and ``z`` (length, Z) float32, the codes that were decoded.  Under data parallelism every rank does everything.
+        attach_instruments and combine_velocity_and_held_notes are refused: the feedback cannot express them (the reference's own
+        assert at vae_definition.py:790 can fire on a decode that is fed back)."""
+        import torch
+        from . import events as ev
+        from . import longsongs as ls
+        from . import packers
+        from . import reconstruction as rec
+        (s, _), sp = self._analysis(rec), self._s.spec
+        p = ls.params(s)
+        packers.refuse_meta_without_instrument(s)
+        self._check_song_extras(note_events, pianoroll)
+        if sp.attach or packers._g(s, "attach_instruments"):
+            raise NotImplementedError("long_songs with attach_instruments: a decoded row does not carry the attached instrument")
+        if packers._g(s, "combine_velocity_and_held_notes"):
+            raise NotImplementedError("long_songs with combine_velocity_and_held_notes: a fed-back decode can break the reference's "
+                                      "own assertion that a held step has no velocity")
+        all_z = np.asarray(all_z)
+        if all_z.dtype != np.float32:
+            raise ValueError("long_songs: all_z is float32, as encoder.predict returns it, got %s" % all_z.dtype)
+        codes = ls._host_codes(codes, "long_songs: the start codes")
+        ls._check_walk(all_z, codes, ())
+        if all_z.shape[1] != sp.Z:
+            raise ValueError("long_songs: all_z has %d columns, the model's latent has %d" % (all_z.shape[1], sp.Z))
+        length = int(length)
+        if length <= 0:
+            raise ValueError("long_songs: length must be positive")
+        e_d, den = ls.pull_factors(np.std(all_z) if e is None else e)
+        S, Z, N = codes.shape[0], sp.Z, all_z.shape[0]
+        sample = self._sample_spec(S * length, sample_method, temperature, seed, None, self._softmax_heads())
+        eps = self._s.epsilon(S * length).reshape(length, S, Z)
+        eng = self._s.get_infer(S)
+        dev = eng.device
+        sink = sinks.LockstepRolls(S, length)
+        with torch.cuda.device(dev):
+            A = torch.from_numpy(np.ascontiguousarray(all_z)).to(dev)
+            start = torch.from_numpy(np.ascontiguousarray(codes)).to(dev)
+            eps_d = torch.from_numpy(np.ascontiguousarray(eps)).to(dev)
+            picked = torch.zeros((S, length), dtype=torch.int32, device=dev)
+            best = torch.empty((length, S), dtype=torch.int32, device=dev)
+            dist = torch.empty((length, S), dtype=torch.float64, device=dev)
+            z_run = torch.empty((length, S, Z), dtype=torch.float32, device=dev)
+            for g0 in range(0, S, eng.maxB):
+                B = min(S, g0 + eng.maxB) - g0
+                work = torch.empty(ls.workspace_bytes(N, B, Z), dtype=torch.uint8, device=dev)
+                # the pulled codes of two iterations: what is written now, and the history of the next one
+                pulled = [torch.empty((B, Z), dtype=torch.float32, device=dev) for _ in range(2)]
+                previous = None
+                for it in range(length):
+                    r_in = start[g0:g0 + B] if it == 0 else None
+                    r_out = torch.empty_like(r_in) if it == 0 else pulled[it & 1]
+                    eng.stage_decoder_walk(B, dict(all_z=A, r_in=r_in, hist_in=previous, picked=picked[g0:g0 + B], n_picked=it, e=e_d,
+                                                   den=den, workspace=work, best_out=best[it, g0:g0 + B], dist_out=dist[it, g0:g0 + B],
+                                                   r_out=r_out))
+                    z_run[it, g0:g0 + B].copy_(eng._v("zh", eng.pad16(B), sp.zin)[:B, :Z])
+                    spec = None if sample is None else dict(sample, first_window=it * S + g0, uniforms={})
+                    eng.decode(B, want_probs=False, sample=spec, want_velocity=sp.meta_velocity)
+                    views = eng.decoded(B, sample is not None)
+                    sink.batch_at(eng, it, g0, B, views)
+                    if it + 1 < length:
+                        eng.stage_encoder_feedback(B, views, eps_d[it, g0:g0 + B], p)
+                        eng.encode(B)
+                    previous = r_out
+            eng.check_pipeline()
+            picked_h, dist_h = picked.cpu().numpy(), dist.cpu().numpy().T
+            z_h = z_run.cpu().numpy().transpose(1, 0, 2)
+        rolls = sink.result()
+        res = self._finish_songs(rolls, [length] * S, None, note_events, close_at_end, None, None, batch_size, pianoroll, carried=False)
+        for k, d in enumerate(res):
+            d.update(picked=picked_h[k].astype(np.int64), distances=np.ascontiguousarray(dist_h[k]), z=np.ascontiguousarray(z_h[k]))
+            if "instr" in d and "programs" not in d:
+                d["programs"] = ev.vote_for_programs(d["instr"], [length], s)[0]
+        return res
 
     def switch_styles(self, zs, classes, S=None, judges=None, note_events=False, batch_size=32, programs=None, close_at_end=False,
                       sample_method="argmax", temperature=None, seed=None):
