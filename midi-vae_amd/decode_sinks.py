@@ -102,8 +102,7 @@ class JudgedSweepStatistics(SweepStatistics):
         with torch.cuda.device(rows.device):
             if vel is not None:
                 after = torch.empty((B, rows.shape[0]), dtype=torch.float32, device=rows.device)
-                sweep.enqueue(rows.data_ptr(), vel.data_ptr(), rows.stride(0), rows.stride(1), B, rows.shape[0], self.p, None, after,
-                              torch.cuda.current_stream().cuda_stream)
+                sweep.enqueue(rows[:, :B].t(), vel[:, :B].t(), self.p, None, after, torch.cuda.current_stream().cuda_stream)
             instr = views["instr"][:, :B].t() if "instr" in views else None
             tables = self.judges.probabilities(rows[:, :B].t(), after, instr, self.batch_size)
             col = torch.full((B, 3), float("nan"), dtype=torch.float32, device=rows.device)
@@ -128,13 +127,17 @@ class SongRolls(Sink):
     def __init__(self, n):
         Sink.__init__(self, n=n, rolls={})
 
-    def batch(self, eng, lo, hi, views):
+    def _copy(self, eng, views, count, rows):
+        """the first ``count`` columns of every buffer of ``views`` to the rows ``rows`` of its roll, allocated on first sight"""
         import torch
         for k in ("notes", "velocity", "held", "instr"):
             if k in views:
                 if k not in self.rolls:
                     self.rolls[k] = torch.empty((self.n, views[k].shape[0]), dtype=views[k].dtype, device=eng.device)
-                self.rolls[k][lo:hi].copy_(views[k][:, :hi - lo].t())
+                self.rolls[k][rows].copy_(views[k][:, :count].t())
+
+    def batch(self, eng, lo, hi, views):
+        self._copy(eng, views, hi - lo, slice(lo, hi))
 
     def result(self):
         return self.rolls
@@ -149,10 +152,4 @@ class LockstepRolls(SongRolls):
         self.length = length
 
     def batch_at(self, eng, it, first_song, count, views):
-        import torch
-        rows = slice(first_song * self.length + it, (first_song + count) * self.length, self.length)
-        for k in ("notes", "velocity", "held", "instr"):
-            if k in views:
-                if k not in self.rolls:
-                    self.rolls[k] = torch.empty((self.n, views[k].shape[0]), dtype=views[k].dtype, device=eng.device)
-                self.rolls[k][rows].copy_(views[k][:, :count].t())
+        self._copy(eng, views, count, slice(first_song * self.length + it, (first_song + count) * self.length, self.length))

@@ -158,9 +158,11 @@ def _tonal_on(device):
     return _tonal_dev[key]
 
 
-def enqueue(ptr, stride_t, stride_w, n, T, p, sig_out, harm_out, tonal, stream):
-    """mvae_desc_windows on device memory the caller owns: ``sig_out`` (n, >= 15) / ``harm_out`` (n, V * V) float64 tensors or None"""
-    a = hl.DescArgs(idx=ptr, stride_t=stride_t, stride_w=stride_w, n=n, T=T, voices=p["voices"], silent=p["silent"],
+def enqueue(idx, p, sig_out, harm_out, tonal, stream):
+    """mvae_desc_windows on device memory the caller owns: ``idx`` (n, T) uint8 tensor view of any strides (a decode's time-major
+    buffer: ``rows[:, :B].t()``), ``sig_out`` (n, >= 15) / ``harm_out`` (n, V * V) float64 tensors or None"""
+    n, T = idx.shape
+    a = hl.DescArgs(idx=idx.data_ptr(), stride_t=idx.stride(1), stride_w=idx.stride(0), n=n, T=T, voices=p["voices"], silent=p["silent"],
                     n_pitch=p["n_pitch"], low_crop=p["low_crop"], resolution=p["resolution"],
                     ld_sig=0 if sig_out is None else sig_out.stride(0), tonal=hl.ptr(tonal), sig_out=hl.ptr(sig_out),
                     harm_out=hl.ptr(harm_out))
@@ -183,8 +185,7 @@ def _device_run(idx, p, want_sig, want_harm, device=None):
     harm = torch.empty((n, V * V), dtype=torch.float64, device=t.device) if want_harm else None
     if n:
         with torch.cuda.device(t.device):
-            enqueue(t.data_ptr(), t.stride(1), t.stride(0), n, T, p, sig, harm, _tonal_on(t.device) if want_harm else None,
-                    torch.cuda.current_stream().cuda_stream)
+            enqueue(t, p, sig, harm, _tonal_on(t.device) if want_harm else None, torch.cuda.current_stream().cuda_stream)
     return (None if sig is None else sig.cpu().numpy(), None if harm is None else harm.cpu().numpy().reshape(n, V, V))
 
 
@@ -197,8 +198,8 @@ def decoded_batch(rows, B, p):
     pack = HostPack(rows.device, [("signature", torch.float64, (B, SIGNATURE_LENGTH)), ("harmonicity", torch.float64, (B, V * V)),
                                   ("notes", torch.uint8, (B, T))])
     with torch.cuda.device(rows.device):
-        enqueue(rows.data_ptr(), rows.stride(0), rows.stride(1), B, T, p, pack.views["signature"], pack.views["harmonicity"],
-                _tonal_on(rows.device), torch.cuda.current_stream().cuda_stream)
+        enqueue(rows[:, :B].t(), p, pack.views["signature"], pack.views["harmonicity"], _tonal_on(rows.device),
+                torch.cuda.current_stream().cuda_stream)
         pack.views["notes"].copy_(rows[:, :B].t())
         res = pack.to_host()
     res["harmonicity"] = res["harmonicity"].reshape(B, V, V)

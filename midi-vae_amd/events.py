@@ -24,7 +24,7 @@ import numpy as np
 from . import hiplib as hl
 from .packers import _g
 from .reconstruction import first_windows
-from .rolls import as_rolls, base_params, check_rows, device_roll, host_roll, sounding
+from .rolls import as_rolls, base_params, check_rows, device_roll, host_roll, sounding, with_strides_of
 
 RECORD = np.dtype([("start", "<i4"), ("end", "<i4"), ("pitch", "u1"), ("voice", "u1"), ("velocity", "<i2")])          # mvae_note_event
 MAX_T = 65536
@@ -208,10 +208,7 @@ def run_on_device(idx, vel, held, song, n_songs, p, close=False):
     dev = idx.device
     if idx.stride(0) <= 0 or idx.stride(1) <= 0:          # (a window axis of one element may carry any stride)
         idx = idx.contiguous()
-    if vel is not None and vel.stride() != idx.stride():
-        vel = torch.empty_strided(idx.shape, idx.stride(), dtype=torch.float32, device=dev).copy_(vel)
-    if held is not None and held.stride() != idx.stride():
-        held = torch.empty_strided(idx.shape, idx.stride(), dtype=torch.uint8, device=dev).copy_(held)
+    vel, held = with_strides_of(idx, vel), with_strides_of(idx, held)
     records = torch.empty(n * T * RECORD.itemsize, dtype=torch.uint8, device=dev)
     offsets = torch.empty(n_songs * p["voices"] + 1, dtype=torch.int32, device=dev)
     total = torch.empty(1, dtype=torch.int32, device=dev)

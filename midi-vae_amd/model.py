@@ -29,6 +29,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import decode_sinks as sinks
+from . import song_decodes as songs
 from .layout import ModelSpec, ParamLayout, init_params, spec_from_create_kwargs
 
 
@@ -605,17 +606,7 @@ class Decoder(_ModelView):
         """the decoder inputs of the n * Z * K windows of a latent sweep, in the order (sample, dimension, value): window (i, d, k)
         is z[i] with coordinate d set to values[k]; C = 0, a zero signature and - the reference decodes every window in a call of
         its own (vae_evaluation.py:1132-1140) - a zero history"""
-        from . import packers
-        sp = self._s.spec
-        z = np.asarray(z, np.float64)
-        if z.ndim != 2 or z.shape[1] != sp.Z:
-            raise ValueError("z must be (n, %d), got %r" % (sp.Z, z.shape))
-        n, Z, K = z.shape[0], sp.Z, len(values)
-        zs = np.repeat(z[:, None, None, :], Z, axis=1).repeat(K, axis=2)
-        zs[:, np.arange(Z), :, np.arange(Z)] = np.asarray(values, np.float64)
-        zs = zs.reshape(n * Z * K, Z)
-        return packers.prepare_decoder_input(s, zs, 0, np.zeros((n * Z * K, int(packers._g(s, "signature_vector_length")))),
-                                             np.zeros(zs.shape))
+        return songs.sweep_inputs(self, z, values, s)
 
     def latent_sweep(self, z, range_end_in_stds=1.0, sigma=1.0, evaluations_per_dimension=5, positive_and_negative=True,
                      batch_size=32, sample_method="argmax", temperature=None, seed=None, return_rolls=False, judges=None):
@@ -633,35 +624,8 @@ class Decoder(_ModelView):
         class-0 probability the pitch, velocity and instrument judge give every window (NaN: no such head or judge) and the
         summaries gain the reference's ``mean_pitchstyle_*``, ``mean_velocitystyle_*`` and ``mean_instrumentstyle_*`` keys
         (:1035-1039, :1089-1093, :1105-1109); one more device-to-host read for the whole run."""
-        from . import packers
-        from . import sweep as sweep_mod
-        (s, p), sp = self._analysis(sweep_mod), self._s.spec
-        values = np.asarray(sweep_mod.sweep_values(range_end_in_stds, sigma, evaluations_per_dimension, positive_and_negative))
-        z = np.asarray(z, np.float64)
-        x = self.sweep_inputs(z, values, s)
-        n, Z, K = z.shape[0], sp.Z, len(values)
-        if n == 0:
-            raise ValueError("z holds no sample")
-        if judges is None:
-            sink = sinks.SweepStatistics(p=p, T=sp.T, return_rolls=return_rolls)
-        else:
-            sink = sinks.JudgedSweepStatistics(p=p, T=sp.T, return_rolls=return_rolls, judges=judges, batch_size=batch_size, style=[])
-        got = self._sampled_run(x, batch_size, sink, sample_method, temperature, seed, None)
-        table = got["table"].reshape(n, Z, K, sweep_mod.N_COLUMNS)
-        if got["instr"] is not None:
-            programs = sweep_mod.programs_of(got["instr"], packers._g(s, "instrument_attach_method")).reshape(n, Z, K, sp.V)
-        else:          # the reference's default I: all piano
-            programs = np.zeros((n, Z, K, sp.V), np.int64)
-        style = got["style"].reshape(n, Z, K, 3) if judges is not None else None
-        summaries, infl, peaked, best = sweep_mod.summarize_sweep(table, programs, style=style)
-        res = dict(table=table, programs=programs, values=values, summaries=summaries, influence=infl, most_peaked=peaked,
-                   overall_best=best)
-        if style is not None:
-            res["style"] = style
-        if return_rolls:
-            res["notes"] = got["notes"].reshape(n, Z, K, sp.T)
-            res["velocity"] = got["velocity"].reshape(n, Z, K, sp.T)
-        return res
+        return songs.latent_sweep(self, z, range_end_in_stds, sigma, evaluations_per_dimension, positive_and_negative, batch_size,
+                                  sample_method, temperature, seed, return_rolls, judges)
 
     def predict_songs(self, xs, batch_size=32, sample_method="argmax", temperature=None, seed=None, uniforms=None, originals=None,
                       note_events=False, close_at_end=False, judges=None, classes=None, pianoroll=False):
@@ -691,101 +655,8 @@ class Decoder(_ModelView):
         given); one more device-to-host read for the whole run.  ``pianoroll``: mvae_pianoroll (midi_vae_amd.pianoroll) draws the
         run's device rolls with the velocities after the rules and every song's dict gains ``pianoroll`` (n_pitch, ticks) float64,
         the reference's prepare_for_drawing(Y, V) of the song; one more read.  Other arguments as predict_note_indices."""
-        from . import packers
-        from . import reconstruction as rec
-        from .rolls import as_rolls
-        (s, p), sp = self._analysis(rec), self._s.spec
-        packers.refuse_meta_without_instrument(s)
-        self._check_song_extras(note_events, pianoroll)
-        xs = [_as_list(x) for x in xs]
-        if not xs:
-            return []
-        if len({len(x) for x in xs}) != 1:
-            raise ValueError("predict_songs: every song must pass the same inputs, in the same order")
-        lengths = [np.asarray(x[1]).shape[0] for x in xs]
-        for i, m in enumerate(lengths):
-            if m <= 0:
-                raise ValueError("predict_songs: song %d has no windows - leave empty songs out of the list" % i)
-        if judges is not None and (classes is None or len(classes) != len(xs)):
-            raise ValueError("predict_songs: judges score every song against its class - pass one class per song")
-        orig = None
-        if originals is not None:
-            originals = [np.asarray(as_rolls(o)) for o in originals]
-            if len(originals) != len(xs):
-                raise ValueError("predict_songs: %d originals for %d songs" % (len(originals), len(xs)))
-            for i, (o, m) in enumerate(zip(originals, lengths)):
-                if o.shape != (m, sp.T):
-                    raise ValueError("predict_songs: the original of song %d has shape %r, expected %r" % (i, o.shape, (m, sp.T)))
-            orig = np.concatenate(originals, 0)
-        x = [np.concatenate([np.asarray(xi[k]) for xi in xs], 0) for k in range(len(xs[0]))]
-        n = int(sum(lengths))
-        rolls = self._sampled_run(x, batch_size, sinks.SongRolls(n), sample_method, temperature, seed, uniforms)
-        return self._finish_songs(rolls, lengths, orig, note_events, close_at_end, judges, classes, batch_size, pianoroll)
-
-    def _check_song_extras(self, note_events, pianoroll):
-        """the refusals of what predict_songs and decode_paths run behind the decode, before anything is decoded"""
-        if note_events:
-            from . import events as ev
-            self._analysis(ev)
-        if pianoroll:
-            from . import pianoroll as pr
-            self._analysis(pr)
-
-    def _finish_songs(self, rolls, lengths, orig, note_events, close_at_end, judges, classes, batch_size, pianoroll, carried=True):
-        """what follows the decode of whole songs, on the run's device rolls (SongRolls): mvae_recon_songs, then as asked
-        mvae_note_events, the style judges and mvae_pianoroll; one dict per song (predict_songs describes it).  ``carried`` False: the
-        velocity rules start afresh in every window (long_songs: the reference post-processes one window a call there)"""
-        import torch
-        from . import reconstruction as rec
-        from .style import style_of
-        (s, p), sp = self._analysis(rec), self._s.spec
-        if note_events:
-            from . import events as ev
-            _, ep = self._analysis(ev)
-        if pianoroll:
-            from . import pianoroll as pr
-            _, pp = self._analysis(pr)
-        n = int(sum(lengths))
-        dev = rolls["notes"].device
-        with torch.cuda.device(dev):
-            first = torch.from_numpy(rec.first_windows(lengths, n)).to(dev)
-            outs = rec.run_on_device(rolls["notes"], rolls.get("velocity"), rolls.get("held"), None if orig is None else torch.from_numpy(orig).to(dev),
-                                     first if carried else None, p)
-            if note_events:
-                ev._check(sp.T, ep, n)
-                song = torch.from_numpy(ev.song_ordinals(lengths, n)).to(dev)
-                table = ev.run_on_device(rolls["notes"], outs[0], outs[1], song, len(lengths), ep, close_at_end)
-            if judges is not None:
-                tables = judges.probabilities(rolls["notes"], outs[0] if "velocity" in rolls else None, rolls.get("instr"), batch_size)
-                style_table, ensemble = judges.score_groups(tables, classes, lengths)
-            if pianoroll:
-                images = pr.split_songs(pr.run_on_device(rolls["notes"], outs[0], first, pp).cpu().numpy(), lengths, sp.T // sp.V)
-            velocity, starts, counts = (t.cpu().numpy() for t in outs)
-            notes = rolls["notes"].cpu().numpy()
-            instr = rolls["instr"].cpu().numpy() if "instr" in rolls else None
-        metrics = rec.song_metrics(counts, lengths, sp.T, s) if orig is not None else None
-        if note_events:
-            with torch.cuda.device(dev):
-                song_events = ev.split_songs(*ev.read_back(table[0], table[1]), sp.V)
-            programs = ev.vote_for_programs(instr, lengths, s) if instr is not None else None
-        res, lo = [], 0
-        for i, m in enumerate(lengths):
-            d = dict(notes=notes[lo:lo + m], velocity=velocity[lo:lo + m], starts=starts[lo:lo + m], counts=counts[lo:lo + m])
-            if instr is not None:
-                d["instr"] = instr[lo:lo + m]
-            if metrics is not None:
-                d["metrics"] = metrics[i]
-            if note_events:
-                d["events"] = song_events[i]
-                if programs is not None:
-                    d["programs"] = programs[i]
-            if judges is not None:
-                d["style"] = dict(style_of(style_table[i]), ensemble_prediction=None if ensemble is None else ensemble[lo:lo + m])
-            if pianoroll:
-                d["pianoroll"] = images[i]
-            res.append(d)
-            lo += m
-        return res
+        return songs.predict_songs(self, xs, batch_size, sample_method, temperature, seed, uniforms, originals, note_events,
+                                   close_at_end, judges, classes, pianoroll)
 
     def decode_paths(self, paths, batch_size=32, sample_method="argmax", temperature=None, seed=None, note_events=False,
                      close_at_end=False, pianoroll=False):
@@ -797,83 +668,35 @@ class Decoder(_ModelView):
         mvae_recon_songs, with ``note_events`` mvae_note_events, with ``pianoroll`` mvae_pianoroll.  One dict per song as
         predict_songs returns it, plus ``z`` (m_i, Z) float32, the latent rows the decoder read (one more call of the kernel into a
         tensor of the whole run).  Other arguments as predict_songs."""
-        import torch
-        from . import generation as gen
-        from . import packers
-        from . import reconstruction as rec
-        (s, _), sp = self._analysis(rec), self._s.spec
-        packers.refuse_meta_without_instrument(s)
-        self._check_song_extras(note_events, pianoroll)
-        paths = list(paths)
-        if not paths:
-            return []
-        run = gen.concat_paths(paths)
-        if int(run["anchors"].shape[1]) != sp.Z:
-            raise ValueError("decode_paths: the anchors have %d columns, the model's latent has %d" % (run["anchors"].shape[1], sp.Z))
-        lengths, n = run["lengths"], len(run["a0"])
-        sample = self._sample_spec(n, sample_method, temperature, seed, None, self._softmax_heads())
-        state = {}
-
-        def fill(eng, lo, hi):
-            if "run" not in state:          # (once per run: the engine, and with it the device, exists from here on)
-                state["run"] = gen.upload(run, eng.device)
-            eng.stage_decoder_paths(hi - lo, lo, state["run"])
-
-        rolls = self._run(None, batch_size, sinks.SongRolls(n), sample, stage=(n, fill))
-        dev = rolls["notes"].device
-        with torch.cuda.device(dev):
-            z_dev = torch.empty((n, sp.Z), dtype=torch.float32, device=dev)
-            gen.enqueue(state["run"], 0, n, z_dev, None, torch.cuda.current_stream().cuda_stream)
-            z = z_dev.cpu().numpy()
-        res = self._finish_songs(rolls, lengths, None, note_events, close_at_end, None, None, batch_size, pianoroll)
-        lo = 0
-        for d, m in zip(res, lengths):
-            d["z"] = z[lo:lo + m]
-            lo += m
-        return res
+        return songs.decode_paths(self, paths, batch_size, sample_method, temperature, seed, note_events, close_at_end, pianoroll)
 
     def interpolation_songs(self, code_pairs, length, mode="lerp", **kw):
         """the reference's random interpolation songs (:841-887): for every pair of codes one song of ``length + 1`` windows;
         ``kw`` as decode_paths"""
-        from . import generation as gen
-        return self.decode_paths([gen.interpolation_path(a, b, length, mode) for a, b in code_pairs], **kw)
+        return songs.interpolation_songs(self, code_pairs, length, mode, **kw)
 
     def medleys(self, list_of_Rs, interpolation_length, mode="lerp", **kw):
         """the reference's medleys (:705-837): for every list of encoded songs ``Rs`` one song - their windows, bridged through
         latent space by ``interpolation_length`` windows; ``kw`` as decode_paths"""
-        from . import generation as gen
-        return self.decode_paths([gen.medley_path(Rs, interpolation_length, mode) for Rs in list_of_Rs], **kw)
+        return songs.medleys(self, list_of_Rs, interpolation_length, mode, **kw)
 
     def random_songs(self, codes, **kw):
         """the reference's random songs (vae_evaluation.py:1771-1785): every row of ``codes`` (n, Z) - drawn by the caller as the
         reference draws them, np.random.normal(0, z_std_train) - is a song of ONE window with C = 0, S = 0 and a zero history; all of
         them are one decode_paths run.  ``kw`` and the song dicts as decode_paths"""
-        from . import generation as gen
-        codes = np.asarray(codes)
-        if codes.ndim != 2 or codes.shape[0] <= 0:
-            raise ValueError("random_songs: codes are (n > 0, Z), got %r" % (codes.shape,))
-        return self.decode_paths([gen.code_path(c) for c in codes], **kw)
+        return songs.random_songs(self, codes, **kw)
 
     @staticmethod
     def class_knob_codes(code, num_classes):
         """(num_classes, Z): row C is ``code`` with the columns 0 .. num_classes-1 set to -1 and column C to 1 (:1793-1797)"""
-        code = np.asarray(code).reshape(-1)
-        if code.dtype not in (np.float32, np.float64):
-            code = code.astype(np.float64)
-        num_classes = int(num_classes)
-        if not 1 <= num_classes <= code.shape[0]:
-            raise ValueError("class_knob_songs: %d classes for a code of %d columns" % (num_classes, code.shape[0]))
-        out = np.repeat(code[None, :], num_classes, 0)
-        out[:, :num_classes] = -1
-        out[np.arange(num_classes), np.arange(num_classes)] = 1
-        return out
+        return songs.class_knob_codes(code, num_classes)
 
     def class_knob_songs(self, code, num_classes, **kw):
         """the reference's class knob (:1787-1814): one random ``code`` (Z,), decoded once per class with the first ``num_classes``
         latent columns turned to that class (class_knob_codes) - ``num_classes`` songs of one window each, in class order, as
         random_songs returns them.  With ``pianoroll=True`` the caller forms pianoroll.difference_image of neighbouring classes
         (the reference's _switchdiff pictures)"""
-        return self.random_songs(self.class_knob_codes(code, num_classes), **kw)
+        return songs.class_knob_songs(self, code, num_classes, **kw)
 
     def long_songs(self, all_z, codes, length=20, e=None, sample_method="argmax", temperature=None, seed=None, note_events=False,
                    pianoroll=False, close_at_end=False, batch_size=32):
@@ -893,76 +716,8 @@ class Decoder(_ModelView):
         (length,) and ``z`` (length, Z) float32, the codes that were decoded.  Under data parallelism every rank does everything.
         attach_instruments and combine_velocity_and_held_notes are refused: the feedback cannot express them (the reference's own
         assert at vae_definition.py:790 can fire on a decode that is fed back)."""
-        import torch
-        from . import events as ev
-        from . import longsongs as ls
-        from . import packers
-        from . import reconstruction as rec
-        (s, _), sp = self._analysis(rec), self._s.spec
-        p = ls.params(s)
-        packers.refuse_meta_without_instrument(s)
-        self._check_song_extras(note_events, pianoroll)
-        if sp.attach or packers._g(s, "attach_instruments"):
-            raise NotImplementedError("long_songs with attach_instruments: a decoded row does not carry the attached instrument")
-        if packers._g(s, "combine_velocity_and_held_notes"):
-            raise NotImplementedError("long_songs with combine_velocity_and_held_notes: a fed-back decode can break the reference's "
-                                      "own assertion that a held step has no velocity")
-        all_z = np.asarray(all_z)
-        if all_z.dtype != np.float32:
-            raise ValueError("long_songs: all_z is float32, as encoder.predict returns it, got %s" % all_z.dtype)
-        codes = ls._host_codes(codes, "long_songs: the start codes")
-        ls._check_walk(all_z, codes, ())
-        if all_z.shape[1] != sp.Z:
-            raise ValueError("long_songs: all_z has %d columns, the model's latent has %d" % (all_z.shape[1], sp.Z))
-        length = int(length)
-        if length <= 0:
-            raise ValueError("long_songs: length must be positive")
-        e_d, den = ls.pull_factors(np.std(all_z) if e is None else e)
-        S, Z, N = codes.shape[0], sp.Z, all_z.shape[0]
-        sample = self._sample_spec(S * length, sample_method, temperature, seed, None, self._softmax_heads())
-        eps = self._s.epsilon(S * length).reshape(length, S, Z)
-        eng = self._s.get_infer(S)
-        dev = eng.device
-        sink = sinks.LockstepRolls(S, length)
-        with torch.cuda.device(dev):
-            A = torch.from_numpy(np.ascontiguousarray(all_z)).to(dev)
-            start = torch.from_numpy(np.ascontiguousarray(codes)).to(dev)
-            eps_d = torch.from_numpy(np.ascontiguousarray(eps)).to(dev)
-            picked = torch.zeros((S, length), dtype=torch.int32, device=dev)
-            best = torch.empty((length, S), dtype=torch.int32, device=dev)
-            dist = torch.empty((length, S), dtype=torch.float64, device=dev)
-            z_run = torch.empty((length, S, Z), dtype=torch.float32, device=dev)
-            for g0 in range(0, S, eng.maxB):
-                B = min(S, g0 + eng.maxB) - g0
-                work = torch.empty(ls.workspace_bytes(N, B, Z), dtype=torch.uint8, device=dev)
-                # the pulled codes of two iterations: what is written now, and the history of the next one
-                pulled = [torch.empty((B, Z), dtype=torch.float32, device=dev) for _ in range(2)]
-                previous = None
-                for it in range(length):
-                    r_in = start[g0:g0 + B] if it == 0 else None
-                    r_out = torch.empty_like(r_in) if it == 0 else pulled[it & 1]
-                    eng.stage_decoder_walk(B, dict(all_z=A, r_in=r_in, hist_in=previous, picked=picked[g0:g0 + B], n_picked=it, e=e_d,
-                                                   den=den, workspace=work, best_out=best[it, g0:g0 + B], dist_out=dist[it, g0:g0 + B],
-                                                   r_out=r_out))
-                    z_run[it, g0:g0 + B].copy_(eng._v("zh", eng.pad16(B), sp.zin)[:B, :Z])
-                    spec = None if sample is None else dict(sample, first_window=it * S + g0, uniforms={})
-                    eng.decode(B, want_probs=False, sample=spec, want_velocity=sp.meta_velocity)
-                    views = eng.decoded(B, sample is not None)
-                    sink.batch_at(eng, it, g0, B, views)
-                    if it + 1 < length:
-                        eng.stage_encoder_feedback(B, views, eps_d[it, g0:g0 + B], p)
-                        eng.encode(B)
-                    previous = r_out
-            eng.check_pipeline()
-            picked_h, dist_h = picked.cpu().numpy(), dist.cpu().numpy().T
-            z_h = z_run.cpu().numpy().transpose(1, 0, 2)
-        rolls = sink.result()
-        res = self._finish_songs(rolls, [length] * S, None, note_events, close_at_end, None, None, batch_size, pianoroll, carried=False)
-        for k, d in enumerate(res):
-            d.update(picked=picked_h[k].astype(np.int64), distances=np.ascontiguousarray(dist_h[k]), z=np.ascontiguousarray(z_h[k]))
-            if "instr" in d and "programs" not in d:
-                d["programs"] = ev.vote_for_programs(d["instr"], [length], s)[0]
-        return res
+        return songs.long_songs(self, all_z, codes, length, e, sample_method, temperature, seed, note_events, pianoroll, close_at_end,
+                                batch_size)
 
     def switch_styles(self, zs, classes, S=None, judges=None, note_events=False, batch_size=32, programs=None, close_at_end=False,
                       sample_method="argmax", temperature=None, seed=None):
@@ -985,94 +740,8 @@ class Decoder(_ModelView):
         the per-window ``ensemble_prediction``) and ``style_target`` (against C_switch); with ``note_events`` ``events`` for
         midifile.write_midi (the held head's index where the model has one, else a note starts where the velocity after the rules
         exceeds the threshold, as packers.process_decoder_indices derives D)."""
-        import torch
-        from . import descriptors, packers
-        from . import events as ev
-        from . import style as style_mod
-        from . import sweep as sweep_mod
-        (s, p), sp = self._analysis(sweep_mod), self._s.spec
-        _, dp = self._analysis(descriptors, True)
-        packers.refuse_meta_without_instrument(s)
-        if note_events:
-            _, ep = self._analysis(ev)
-        zs = [np.asarray(z, np.float64) for z in zs]
-        if len(classes) != len(zs) or (S is not None and len(S) != len(zs)) or (programs is not None and len(programs) != len(zs)):
-            raise ValueError("switch_styles: one class (and one signature array, one program list) per song")
-        for i, z in enumerate(zs):
-            if z.ndim != 2 or z.shape[0] <= 0 or z.shape[1] != sp.Z:
-                raise ValueError("switch_styles: the latents of song %d have shape %r, expected (m > 0, %d)" % (i, z.shape, sp.Z))
-            if not 0 <= int(classes[i]) < sp.C:
-                raise ValueError("switch_styles: song %d has class %r, the model has %d" % (i, classes[i], sp.C))
-        pairs = style_mod.switch_pairs(classes, sp.C)
-        if not pairs:
-            return dict(pairs=[], switch_instruments_matrix=None)
-        SD = int(packers._g(s, "signature_vector_length"))
-        xs = []
-        for song, C, C_switch in pairs:
-            switched, history = style_mod.switched_latents(zs[song], C, C_switch)
-            sig = np.zeros((switched.shape[0], SD)) if S is None else np.asarray(S[song])
-            xs.append(packers.prepare_decoder_input(s, switched, C_switch, sig, history))           # :2481
-        x = [np.concatenate([np.asarray(xi[k]) for xi in xs], 0) for k in range(len(xs[0]))]
-        lengths = [zs[song].shape[0] for song, _, _ in pairs]
-        n = int(sum(lengths))
-        rolls = self._sampled_run(x, batch_size, sinks.SongRolls(n), sample_method, temperature, seed, None)
-        notes_d, dev = rolls["notes"], rolls["notes"].device
-        V = sp.V
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream().cuda_stream
-            vel_d = None
-            if "velocity" in rolls:
-                vel_d = torch.empty((n, sp.T), dtype=torch.float32, device=dev)
-                sweep_mod.enqueue(notes_d.data_ptr(), rolls["velocity"].data_ptr(), notes_d.stride(1), notes_d.stride(0), n, sp.T, p, None,
-                                  vel_d, stream)
-            sig_d = torch.empty((n, descriptors.SIGNATURE_LENGTH), dtype=torch.float64, device=dev)
-            harm_d = torch.empty((n, V * V), dtype=torch.float64, device=dev)
-            descriptors.enqueue(notes_d.data_ptr(), notes_d.stride(1), notes_d.stride(0), n, sp.T, dp, sig_d, harm_d,
-                                descriptors._tonal_on(dev), stream)
-            if judges is not None:
-                tables = judges.probabilities(notes_d, vel_d, rolls.get("instr"), batch_size)
-                own = np.asarray([C for _, C, _ in pairs])
-                target = np.asarray([t for _, _, t in pairs])
-                style_table, ensemble = judges.score_groups(tables, own, lengths)
-                target_table, _ = judges.score_groups(tables, target, lengths)
-            if note_events:
-                ev._check(sp.T, ep, n)
-                song_of = torch.from_numpy(ev.song_ordinals(lengths, n)).to(dev)
-                if "held" in rolls:
-                    starts = rolls["held"]
-                elif vel_d is not None:
-                    starts = (~(vel_d.double() > p["threshold"])).to(torch.uint8)
-                else:
-                    starts = torch.ones((n, sp.T), dtype=torch.uint8, device=dev)
-                ev_table = ev.run_on_device(notes_d, vel_d, starts, song_of, len(lengths), ep, close_at_end)
-                song_events = ev.split_songs(*ev.read_back(ev_table[0], ev_table[1]), V)
-            notes = notes_d.cpu().numpy()
-            velocity = vel_d.cpu().numpy() if vel_d is not None else np.full((n, sp.T), p["default_velocity"], np.float32)
-            signature, harmonicity = sig_d.cpu().numpy(), harm_d.cpu().numpy().reshape(n, V, V)
-            instr = rolls["instr"].cpu().numpy() if "instr" in rolls else None
-        # (without the instrument head the reference decodes its default I, all piano, and votes on that)
-        voted = ev.vote_for_programs(instr, lengths, s) if instr is not None else [[0] * V for _ in pairs]
-        out, lo = [], 0
-        for k, ((song, C, C_switch), m) in enumerate(zip(pairs, lengths)):
-            d = dict(song=song, C=C, C_switch=C_switch, notes=notes[lo:lo + m], velocity=velocity[lo:lo + m],
-                     signature=signature[lo:lo + m], harmonicity=harmonicity[lo:lo + m])
-            if instr is not None:
-                d.update(instr=instr[lo:lo + m], voted_programs=voted[k])
-            if programs is not None:
-                original = [int(v) for v in programs[song]]
-                flag, used = style_mod.instruments_switched(original, voted[k], instr is not None)
-                d.update(instruments_switched=flag, programs=used)
-            if judges is not None:
-                d["style"] = dict(style_mod.style_of(style_table[k]), ensemble_prediction=None if ensemble is None else ensemble[lo:lo + m])
-                d["style_target"] = style_mod.style_of(target_table[k])
-            if note_events:
-                d["events"] = song_events[k]
-            out.append(d)
-            lo += m
-        matrix = None
-        if programs is not None:
-            matrix = style_mod.switch_instruments_matrix(pairs, [[int(v) for v in pr] for pr in programs], voted, sp.C)
-        return dict(pairs=out, switch_instruments_matrix=matrix)
+        return songs.switch_styles(self, zs, classes, S, judges, note_events, batch_size, programs, close_at_end, sample_method,
+                                   temperature, seed)
 
     def predict_indices(self, x, batch_size=32, sample_method="argmax", temperature=None, seed=None, uniforms=None):
         """The decoded index of EVERY softmax head - dict 'notes' (n, T), 'instr' (n, max_voices), 'held' (n, T), 'next' (n, T)

@@ -24,7 +24,7 @@ import numpy as np
 from . import hiplib as hl
 from .packers import _g
 from .reconstruction import first_windows
-from .rolls import as_rolls, base_params, check_rows, device_roll, host_roll, sounding
+from .rolls import as_rolls, base_params, check_rows, device_roll, host_roll, sounding, with_strides_of
 
 MAX_T = 65536
 
@@ -98,8 +98,7 @@ def run_on_device(idx, vel, first, p):
     dev = idx.device
     if idx.stride(0) <= 0 or idx.stride(1) <= 0:
         idx = idx.contiguous()
-    if vel is not None and vel.stride() != idx.stride():
-        vel = torch.empty_strided(idx.shape, idx.stride(), dtype=torch.float32, device=dev).copy_(vel)
+    vel = with_strides_of(idx, vel)
     img = torch.empty((n * (T // p["voices"]), p["n_pitch"]), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         enqueue(idx, vel, first, p, img, torch.cuda.current_stream().cuda_stream)

@@ -22,7 +22,7 @@ import numpy as np
 
 from . import hiplib as hl
 from .packers import _g
-from .rolls import as_rolls, base_params, carried_velocity_rule, check_rows, device_roll, host_roll, sounding
+from .rolls import as_rolls, base_params, carried_velocity_rule, check_rows, device_roll, host_roll, sounding, with_strides_of
 
 COUNTS = ("original_notes", "predicted_notes", "correct_notes", "not_predicted_notes", "new_predicted_notes", "note_starts",
           "note_starts_on_silent_prediction", "note_starts_on_silent_original")
@@ -121,10 +121,7 @@ def run_on_device(idx, vel, held, orig, first, p):
     dev = idx.device
     fix = lambda t: t if t is None or (t.stride(0) > 0 and t.stride(1) > 0) else t.contiguous()
     idx, orig = fix(idx), fix(orig)
-    if vel is not None and vel.stride() != idx.stride():
-        vel = torch.empty_strided(idx.shape, idx.stride(), dtype=torch.float32, device=dev).copy_(vel)
-    if held is not None and held.stride() != idx.stride():
-        held = torch.empty_strided(idx.shape, idx.stride(), dtype=torch.uint8, device=dev).copy_(held)
+    vel, held = with_strides_of(idx, vel), with_strides_of(idx, held)
     vel_out = torch.empty((n, T), dtype=torch.float32, device=dev)
     start_out = torch.empty((n, T), dtype=torch.uint8, device=dev)
     counts = torch.empty((n, N_COUNTS), dtype=torch.int32, device=dev)

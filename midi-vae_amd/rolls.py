@@ -76,6 +76,14 @@ def device_roll(a, dtype, what, shape=None, strides_of=None, device=None):
     return t
 
 
+def with_strides_of(idx, roll):
+    """the optional device roll ``roll`` (None passes through) at the strides of ``idx``: itself, or a copy laid out like ``idx``"""
+    import torch
+    if roll is None or roll.stride() == idx.stride():
+        return roll
+    return torch.empty_strided(idx.shape, idx.stride(), dtype=roll.dtype, device=idx.device).copy_(roll)
+
+
 def host_roll(a, dtype, what, shape=None):
     """the host counterpart: (n, T) uint8 index rolls (whatever as_rolls takes) or float32 values, from a host array or a device
     tensor; None passes through, as in device_roll"""

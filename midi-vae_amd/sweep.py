@@ -109,10 +109,12 @@ def _mirror(idx, vel, p):
 
 
 # ---- the device path -----------------------------------------------------------------------------------------------------------
-def enqueue(idx_ptr, vel_ptr, stride_t, stride_w, n, T, p, stats_out, vel_out, stream):
-    """mvae_sweep_windows on device memory the caller owns: ``stats_out`` (n, >= 22) float64 / ``vel_out`` (n, T) float32
-    contiguous tensors or None; ``vel_ptr`` 0 / None for a model without the velocity head"""
-    a = hl.SweepArgs(idx=idx_ptr, stride_t=stride_t, stride_w=stride_w, vel=vel_ptr or None, n=n, T=T, voices=p["voices"],
+def enqueue(idx, vel, p, stats_out, vel_out, stream):
+    """mvae_sweep_windows on device memory the caller owns.  ``idx`` (n, T) uint8 tensor view of any strides (a decode's time-major
+    buffer: ``rows[:, :B].t()``), ``vel`` a float32 tensor of the same strides or None for a model without the velocity head,
+    ``stats_out`` (n, >= 22) float64 / ``vel_out`` (n, T) float32 contiguous tensors or None."""
+    n, T = idx.shape
+    a = hl.SweepArgs(idx=idx.data_ptr(), stride_t=idx.stride(1), stride_w=idx.stride(0), vel=hl.ptr(vel), n=n, T=T, voices=p["voices"],
                      silent=p["silent"], n_pitch=p["n_pitch"], count_a=p["count_a"], count_b=p["count_b"],
                      override_rules=int(p["override"]), threshold=p["threshold"], default_velocity=p["default_velocity"],
                      ld_out=0 if stats_out is None else stats_out.stride(0), stats_out=hl.ptr(stats_out), vel_out=hl.ptr(vel_out))
@@ -129,8 +131,7 @@ def _device_run(idx, vel, p, want_velocity, device=None):
     roll = torch.empty((n, T), dtype=torch.float32, device=t.device) if want_velocity else None
     if n:
         with torch.cuda.device(t.device):
-            enqueue(t.data_ptr(), None if v is None else v.data_ptr(), t.stride(1), t.stride(0), n, T, p, stats, roll,
-                    torch.cuda.current_stream().cuda_stream)
+            enqueue(t, v, p, stats, roll, torch.cuda.current_stream().cuda_stream)
     return stats.cpu().numpy(), (None if roll is None else roll.cpu().numpy())
 
 
@@ -149,8 +150,8 @@ def decoded_batch(rows, vel, instr, B, p, return_rolls=False):
         blocks += [("velocity", torch.float32, (B, T)), ("notes", torch.uint8, (B, T))]
     pack = HostPack(rows.device, blocks)
     with torch.cuda.device(rows.device):
-        enqueue(rows.data_ptr(), None if vel is None else vel.data_ptr(), rows.stride(0), rows.stride(1), B, T, p, pack.views["table"],
-                pack.views.get("velocity"), torch.cuda.current_stream().cuda_stream)
+        enqueue(rows[:, :B].t(), None if vel is None else vel[:, :B].t(), p, pack.views["table"], pack.views.get("velocity"),
+                torch.cuda.current_stream().cuda_stream)
         if instr is not None:
             pack.views["instr"].copy_(instr[:, :B].t())
         if return_rolls:

@@ -126,7 +126,7 @@ def test_fixture_windows_time_major_padded(fx):
     ar.commit()
     sig, harm = b_sig.t.view(torch.float64), b_harm.t.view(torch.float64)
     assert sig.shape == (Bp, 15) and harm.shape == (Bp, V * V) and sig.data_ptr() == b_sig.t.data_ptr()
-    de.enqueue(b_idx.t.data_ptr(), Bp, 1, B, T, p, sig, harm, b_ton.t, torch.cuda.current_stream().cuda_stream)
+    de.enqueue(b_idx.t[:, :B].t(), p, sig, harm, b_ton.t, torch.cuda.current_stream().cuda_stream)
     ar.fetch()
     ar.assert_guards_intact()
     for b in (b_sig, b_harm):

@@ -107,7 +107,7 @@ def test_fixture_windows_time_major_padded_guarded(fx):
     ar.commit()
     stats = b_stats.t.view(torch.float64)
     assert stats.shape == (Bp, LD) and stats.data_ptr() == b_stats.t.data_ptr()
-    sw.enqueue(b_idx.t.data_ptr(), b_vel.t.data_ptr(), Bp, 1, B, T, p, stats, b_roll.t, torch.cuda.current_stream().cuda_stream)
+    sw.enqueue(b_idx.t[:, :B].t(), b_vel.t[:, :B].t(), p, stats, b_roll.t, torch.cuda.current_stream().cuda_stream)
     ar.fetch()
     ar.assert_guards_intact()
     ar.assert_written(b_roll, np.s_[:B])
@@ -202,8 +202,8 @@ def test_one_output_at_a_time(fx):
     stream = torch.cuda.current_stream().cuda_stream
     stats = torch.full((n, 22), -7.0, dtype=torch.float64, device=DEV)
     roll = torch.full((n, T), -7.0, dtype=torch.float32, device=DEV)
-    sw.enqueue(idx.data_ptr(), vel.data_ptr(), 1, T, n, T, p, stats, None, stream)
-    sw.enqueue(idx.data_ptr(), vel.data_ptr(), 1, T, n, T, p, None, roll, stream)
+    sw.enqueue(idx, vel, p, stats, None, stream)
+    sw.enqueue(idx, vel, p, None, roll, stream)
     assert_table(stats.cpu().numpy(), fx["mirror"][:n], "stats_out alone")
     assert np.array_equal(roll.cpu().numpy().view(np.uint32), fx["mirror_roll"][:n].view(np.uint32))
 

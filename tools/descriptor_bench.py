@@ -74,7 +74,7 @@ def main():
     stream = torch.cuda.current_stream().cuda_stream
 
     def kernel_ms(t, so, ho):
-        run = lambda: de.enqueue(t.data_ptr(), t.stride(1), t.stride(0), n, T, p, so, ho, tonal if ho is not None else None, stream)
+        run = lambda: de.enqueue(t, p, so, ho, tonal if ho is not None else None, stream)
         run()
         torch.cuda.synchronize()
         out = []

@@ -118,14 +118,14 @@ def main():
     vel = rng.random((n, T)).astype(np.float32)
     stats = torch.empty((n, sw.N_COLUMNS), dtype=torch.float64, device="cuda")
     stream = torch.cuda.current_stream().cuda_stream
-    layouts = {"window-major (staged)": (torch.from_numpy(idx).cuda(), torch.from_numpy(vel).cuda(), 1, T),
-               "time-major (direct)  ": (torch.from_numpy(np.ascontiguousarray(idx.T)).cuda(), torch.from_numpy(np.ascontiguousarray(vel.T)).cuda(), n, 1)}
-    for name, (ti, tv, st, swd) in layouts.items():
+    layouts = {"window-major (staged)": (torch.from_numpy(idx).cuda(), torch.from_numpy(vel).cuda()),
+               "time-major (direct)  ": (torch.from_numpy(np.ascontiguousarray(idx.T)).cuda().t(), torch.from_numpy(np.ascontiguousarray(vel.T)).cuda().t())}
+    for name, (ti, tv) in layouts.items():
         ms = []
         for r in range(args.repeats + 2):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            sw.enqueue(ti.data_ptr(), tv.data_ptr(), st, swd, n, T, p, stats, None, stream)
+            sw.enqueue(ti, tv, p, stats, None, stream)
             e1.record()
             e1.synchronize()
             if r >= 2:
